@@ -8,7 +8,13 @@ batch.  Multi-GPU: one process per GPU (torchrun), rows sharded with no
 collective ("weak": every rank predicts its own 1M rows); value = all ranks'
 rows / max-over-ranks wall time.
 
-Also reported (rank 0):
+A plain run sets up, warms up (the device first, with at most PRE_LAUNCHES
+untimed one-stream launches), times the --steps steps and prints the result
+line (value, ms_per_step); --dump-outputs DIR also writes the last timed step's
+predictions to DIR/predict.npy, the same inputs on every run of the same
+arguments.  Every other leg below runs, and its options count, under --full.
+
+With --full also reported (rank 0):
   roofline     -- the resource that binds the C2 kernel:
                   the busiest of VALU issue, the LDS array and the TD in the
                   committed rocprofv3 PMC pass of the same kernel
@@ -124,6 +130,14 @@ def parse_args(argv=None):
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--rows", type=int, default=ROWS)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also run every other leg (one-stream pass and "
+                        "roofline, output check, latency, NaN variant, tree shard, host "
+                        "pipeline, --configs, C5 over HTTP, CPU baselines); a plain run "
+                        "times the headline alone and the options of those legs do nothing")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="write what the last timed step computed to DIR/<name>.npy "
+                        "(float32; a fixed seeded sample of the rows past 64 MB in all)")
     p.add_argument("--nan-variant", type=float, default=0.01,
                    help="also time the same batch with this fraction of NaN features "
                         "(SURVEY.md 8(d) C2 1%%-NaN variant; 0 = skip)")
@@ -1113,6 +1127,36 @@ def c4_cpu(raw_trees, target_s):
 
 
 # ------------------------------------------------------------------- main
+def headline_only(args):
+    """The arguments of a plain run (no --full): every leg beside the headline
+    switched off, whatever its own option says."""
+    a = argparse.Namespace(**vars(args))
+    a.latency_qps = a.nan_variant = a.host_rows = a.host_rows_configs = 0
+    a.configs = a.c5_http_qps = a.c5_http_v2_qps = ""
+    a.no_tree_shard = a.no_cpu_baseline = True
+    return a
+
+
+DUMP_BYTES = 64 << 20
+PRE_LAUNCHES = 200         # most one-stream launches a plain run makes before its warmup
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1):
+    """--dump-outputs: each array (rows first) as DIR/<name>.npy, float32
+    unless it is float64; rank r > 0 writes <name>_rank<r>.npy.  All ranks'
+    files together stay within DUMP_BYTES: of a larger array a fixed sample of
+    the rows (seed 0, in row order) is kept."""
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_BYTES // max(1, world) // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        keep = budget // max(1, a.itemsize * int(np.prod(a.shape[1:], dtype=np.int64)))
+        if a.shape[0] > keep:
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(dirname, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
+
+
 def run(args, device="cuda", backend="nccl", make_engine=None):
     """The rank logic of bench.py.  `make_engine(forest)` returns an object with
     predict_device / predict / info / close (DeviceForest on the GPU; the CPU
@@ -1120,6 +1164,8 @@ def run(args, device="cuda", backend="nccl", make_engine=None):
     import torch
     import torch.distributed as dist
 
+    if not args.full:
+        args = headline_only(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1160,8 +1206,10 @@ def run(args, device="cuda", backend="nccl", make_engine=None):
     outs = [out] + [torch.empty_like(out) for _ in range(n_str - 1)]
 
     last_x = [None] * n_str     # the X buffer each stream's last launch read
+    last_k = [0]                # the stream of the last launch
 
     def launch(k):
+        last_k[0] = k
         last_x[k] = it[0] % len(Xs)
         Xi = Xs[last_x[k]]
         it[0] += 1
@@ -1187,15 +1235,27 @@ def run(args, device="cuda", backend="nccl", make_engine=None):
         return ((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 if device != "cpu" else None)
 
-    # K steps on one stream: the kernel's own launch duration (events on the
-    # stream it runs on), which the roofline and the rocprof summary price
-    for _ in range(args.warmup):
-        step1()
-    wall1, kernel_ms = timed_steps(step1, args.steps, dev_sync, events())
-    if kernel_ms is None:
-        kernel_ms = wall1 / args.steps * 1e3
-    wall1 = max_over_ranks(wall1, device)
-    wall = wall1
+    full = args.full
+    wall = wall1 = kernel_ms = None
+    if full or n_str == 1:
+        # K steps on one stream: the kernel's own launch duration (events on the
+        # stream it runs on), which the roofline and the rocprof summary price.
+        # With one stream this pass is the headline; with more, a pass of its
+        # own that only --full times
+        for _ in range(args.warmup):
+            step1()
+        wall1, kernel_ms = timed_steps(step1, args.steps, dev_sync, events())
+        if kernel_ms is None:
+            kernel_ms = wall1 / args.steps * 1e3
+        wall1 = max_over_ranks(wall1, device)
+        wall = wall1
+    else:
+        # a plain run keeps that pass's launches, untimed, so the headline starts
+        # from the device state it always has (without them it read 2-5 % lower
+        # at 20 steps, 1 % at 100, nothing at 200: hence the cap)
+        for _ in range(min(args.warmup + args.steps, PRE_LAUNCHES)):
+            step1()
+        dev_sync()
     if n_str > 1:
         # the headline: the same K steps with S batches in flight, so one
         # batch's binning and tail overlap the previous batch's walk
@@ -1206,10 +1266,16 @@ def run(args, device="cuda", backend="nccl", make_engine=None):
     # each stream's last output against a one-stream predict of the batch it
     # read (every X buffer is a distinct batch): no batch in flight was
     # skipped, cut short or written by the other stream
-    outputs_identical = streams_match(dev, Xs, outs, last_x, rows, sh, dev_sync, device != "cpu")
+    if args.dump_outputs:
+        # the last timed step's output, before any later leg writes the buffers
+        dump_outputs(args.dump_outputs, {"predict": outs[last_k[0]].cpu().numpy()}, rank, world)
+    outputs_identical = None
+    if full:
+        outputs_identical = streams_match(dev, Xs, outs, last_x, rows, sh, dev_sync,
+                                          device != "cpu")
     value = rows * world * args.steps / wall
     two_stream = None
-    if n_str > 1:
+    if full and n_str > 1:
         two_stream = batch_latency_events(launch, n_str, strs, args.steps, dev_sync)
 
     # the serving-latency leg runs right after the headline, before the legs
@@ -1350,6 +1416,10 @@ def run(args, device="cuda", backend="nccl", make_engine=None):
                        "features": N_FEAT, "layout": LAYOUT_NAMES.get(info["layout"]),
                        "parallelism": f"rows sharded x{world}", "x_buffers": len(Xs),
                        "streams": n_str},
+            "full": full,
+        }
+    if line is not None and full:
+        line.update({
             "single_stream": {"ms_per_step": wall1 / args.steps * 1e3,
                               "value": rows * world * args.steps / wall1,
                               "kernel_ms": kernel_ms},
@@ -1364,7 +1434,7 @@ def run(args, device="cuda", backend="nccl", make_engine=None):
             "tree_shard": tree_shard,
             "c5_http": c5_http,
             "c5_http_v2": c5_http_v2,
-        }
+        })
         line.update(configs)
         line.update(host_configs)
     return line

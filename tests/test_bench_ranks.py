@@ -55,7 +55,7 @@ def _worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE=str(world),
                       RANK=str(rank), LOCAL_RANK=str(rank))
     import bench
-    args = bench.parse_args(["--steps", "5", "--warmup", "1", "--rows", "4096",
+    args = bench.parse_args(["--full", "--steps", "5", "--warmup", "1", "--rows", "4096",
                              "--configs", "c3", "--rows3", "1000", "--config-steps", "2",
                              "--no-cpu-baseline", "--latency-qps", "0",
                              "--host-rows-configs", "1000"])
@@ -122,7 +122,7 @@ def test_bench_cli_gpus_n_starts_n_ranks():
     env["OMP_NUM_THREADS"] = "4"                           # the job's host share
     env.pop("BENCH_HOST_THREADS", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--device", "cpu",
-           "--engine", "tests.bench_stub:make", "--steps", "5", "--warmup", "1",
+           "--full", "--engine", "tests.bench_stub:make", "--steps", "5", "--warmup", "1",
            "--rows", "2048", "--configs", "c3", "--rows3", "2000", "--config-steps", "1",
            "--cpu-seconds", "0.2", "--latency-qps", "200", "--latency-seconds", "0.5",
            "--nan-variant", "0", "--host-rows", "0", "--host-rows-configs", "0"]
@@ -174,7 +174,7 @@ def test_bench_cli_world2_c5_scales_and_tree_shard_checks():
     env["OMP_NUM_THREADS"] = "4"
     http = os.path.exists(bs.LOADGEN)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--device", "cpu",
-           "--engine", "tests.bench_stub:make_canon", "--steps", "2", "--warmup", "1",
+           "--full", "--engine", "tests.bench_stub:make_canon", "--steps", "2", "--warmup", "1",
            "--rows", "1024", "--configs", "", "--no-cpu-baseline", "--latency-qps", "0",
            "--nan-variant", "0", "--host-rows", "0", "--c5-http-v2-qps", "",
            "--c5-http-qps", "100,200" if http else "", "--c5-http-cpu",

@@ -41,7 +41,8 @@ def test_headline_two_streams_same_outputs():
     """The headline's batches in flight (--streams 2) compute every row: each
     stream's output equals the others' bit for bit, the one-stream kernel time
     is reported beside, and value = rows x steps / the multi-stream wall."""
-    args = bench.parse_args(["--steps", "6", "--warmup", "2", "--rows", "262144", "--configs", "",
+    args = bench.parse_args(["--full", "--steps", "6", "--warmup", "2", "--rows", "262144",
+                             "--configs", "",
                              "--no-cpu-baseline", "--latency-qps", "0", "--host-rows", "0",
                              "--nan-variant", "0", "--streams", "2"])
     line = bench.run(args)
@@ -51,6 +52,34 @@ def test_headline_two_streams_same_outputs():
     assert ss["kernel_ms"] > 0 and ss["ms_per_step"] > 0
     assert abs(line["value"] - 262144 * 6 / (line["ms_per_step"] * 6e-3)) < 1e-6 * line["value"]
     assert line["roofline"]["kernel_ms"] == ss["kernel_ms"]
+
+
+def test_plain_run_dumps_last_step_outputs(tmp_path):
+    """A plain run (no --full) times the two-stream headline alone, and
+    --dump-outputs writes the last timed step's predictions: 5 untimed
+    one-stream launches, then warmup 1 + 4 steps rotate over the 3 batches,
+    so the last (10th) launch read the first again (rank 0's seeded host
+    batch), whose predict through the host path is the same kernel on the
+    same rows."""
+    import numpy as np
+    from kfserving_amd.engine import DeviceForest
+    from kfserving_amd.forest import OUT_PREDICT
+    rows = 65537
+    args = bench.parse_args(["--gpus", "1", "--steps", "4", "--warmup", "1", "--rows", str(rows),
+                             "--dump-outputs", str(tmp_path)])
+    line = bench.run(args)
+    assert line["full"] is False and line["steps"] == 4 and line["config"]["streams"] == 2
+    assert "roofline" not in line and "single_stream" not in line and "c3" not in line
+    assert abs(line["value"] - rows * 4 / (line["ms_per_step"] * 4e-3)) < 1e-6 * line["value"]
+    got = np.load(tmp_path / "predict.npy")
+    assert got.dtype == np.float32 and got.shape == (rows,)
+    X = np.random.default_rng(1000).standard_normal((rows, bench.N_FEAT), dtype=np.float32)
+    dev = DeviceForest(bench.build_model()[2], devices=[0])
+    try:
+        want = np.asarray(dev.predict(X, OUT_PREDICT)).reshape(-1)
+    finally:
+        dev.close()
+    assert np.array_equal(got, want)
 
 
 @pytest.mark.parametrize("key", ["c2", "c2_hist", "c3", "c3_f64", "c3_maxbin", "c4"])

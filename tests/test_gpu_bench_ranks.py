@@ -26,7 +26,7 @@ def _rank(rank, port, q):
                       RANK=str(rank), LOCAL_RANK="0")
     try:
         import bench
-        args = bench.parse_args(["--steps", "4", "--warmup", "1", "--rows", "65536",
+        args = bench.parse_args(["--full", "--steps", "4", "--warmup", "1", "--rows", "65536",
                                  "--configs", "c3", "--rows3", "200000", "--config-steps", "1",
                                  "--no-cpu-baseline", "--latency-qps", "0", "--host-rows", "0",
                                  "--nan-variant", "0", "--c5-http-qps", "5000",
