@@ -47,6 +47,15 @@
  *     (static_cast<int> yields INT_MIN there on x86, which LightGBM sends right);
  *     go left iff v / 32 < cat_nwords[n] and bit v % 32 of
  *     cat_bits[cat_offset[n] + v / 32] is set (Common::FindInBitset).
+ *   XGBoost categorical nodes (flags[n] & TI_NODE_CATEGORICAL and
+ *   TI_NODE_CAT_XGB; xgboost >= 1.7 common::Decision / GetNextNode,
+ *   split_type 1) use the same bitsets with another rule:
+ *     if x is NaN:            go left iff flags[n] & TI_NODE_NAN_LEFT
+ *     else if x < 0 or x >= 2^24 (kMaxCat; -0.0 is valid): go left (invalid
+ *                             category)
+ *     else v = (int)x truncated toward zero; go RIGHT iff v / 32 <
+ *     cat_nwords[n] and bit v % 32 of cat_bits[cat_offset[n] + v / 32] is set.
+ *   threshold[n] of a categorical node is unused.
  *   The host encodes each library's rule into threshold/flags:
  *     XGBoost  (x < t, f32)  : threshold = nextafterf(t, -inf) (NaN if t=-inf),
  *                              NAN_LEFT = default_left
@@ -65,7 +74,7 @@
 extern "C" {
 #endif
 
-#define TI_ABI_VERSION 4
+#define TI_ABI_VERSION 5
 
 /* return codes */
 #define TI_OK               0
@@ -83,6 +92,8 @@ extern "C" {
 #define TI_NODE_NAN_LEFT   0x01  /* NaN input goes left                    */
 #define TI_NODE_ZERO_FLIP  0x02  /* x == 0 takes the opposite of (0 <= t)  */
 #define TI_NODE_CATEGORICAL 0x04 /* bitset membership split (LightGBM)     */
+#define TI_NODE_CAT_XGB    0x08  /* ABI 5, with TI_NODE_CATEGORICAL only:  */
+                                 /* XGBoost's rule (in set -> right)       */
 
 /* output transforms applied after accumulation (ti_forest_desc.transform) */
 #define TI_TRANSFORM_IDENTITY    0
@@ -154,21 +165,23 @@ typedef struct ti_forest_info {
   int32_t layout;             /* 0 heap (complete, LDS-staged), 1 explicit nodes,
                                  3 binned heap, 6 record explicit (gathered), 7 staged
                                  records, 8 heap tops + gathered records, 9 heap tops +
-                                 staged records (2, 4 and 5 were
-                                 retired in round 3)                                 */
+                                 staged records, 10 categorical heap (LDS-staged, the
+                                 bitsets inside each tree's block) (DESIGN.md section 3;
+                                 2, 4 and 5 were retired in round 3)                 */
   int32_t depth;              /* heap depth D, or max depth for explicit             */
   int32_t n_trees;
   int32_t n_groups;
   int32_t n_features;
   int32_t n_devices;
   int64_t device_bytes;       /* forest bytes resident per device                   */
-  int64_t tree_stride_bytes;  /* heap layout: bytes per staged tree                 */
+  int64_t tree_stride_bytes;  /* heap layouts (0, 3, 10): bytes per staged tree     */
   int32_t walk;               /* binned heap walk of float32 input: 0 indexed step
                                  (5 VALU), 1 fixed-layout step (4 VALU),
                                  2 fixed-layout step with the scalar-loaded root     */
   int32_t bin_bits;           /* 8 or 16: bin width of the float32 image (0: none)   */
   int32_t tree_ilp;           /* record layouts: trees walked at once per lane       */
-  int32_t n_stages;           /* staged layouts (7, 9): LDS stages of the forest     */
+  int32_t n_stages;           /* staged layouts (7, 9, 10): LDS stages of the forest
+                                 (10: of a float32 batch)                            */
   int32_t top_depth;          /* layouts 8, 9: levels of each tree's heap top        */
   int32_t bottom;             /* layout 9: 0 records, 1 compact u8 nodes (plan_tx8),
                                  2 compact u16 nodes, 3 compact u16 nodes walked two

@@ -35,6 +35,7 @@
 #include "treeinfer.h"
 #include "treeinfer_kernels.h"
 #include "treeinfer_dispatch.h"
+#include "treeinfer_cheap.h"
 
 using ti::ExpNode;
 using ti::HeapNode;
@@ -529,6 +530,17 @@ uint32_t make_meta(int32_t feature, uint8_t flags) {
   return m;
 }
 
+// a categorical node's meta (layouts 1 and 10): LightGBM's rule reads no flag;
+// XGBoost's keeps the default child in the NaN bit
+uint32_t make_cat_meta(uint32_t feature_field, uint8_t flags) {
+  uint32_t m = (feature_field & ti::kMetaFeatMask) | ti::kMetaCat;
+  if (flags & TI_NODE_CAT_XGB) {
+    m |= ti::kMetaCatXgb;
+    if (flags & TI_NODE_NAN_LEFT) m |= ti::kMetaNanLeft;
+  }
+  return m;
+}
+
 // padded heap node below a shallow leaf: always left (x <= +inf, NaN left)
 constexpr uint32_t kPadMeta = ti::kMetaNanLeft;
 
@@ -606,7 +618,7 @@ struct ti_forest {
   int32_t zero_rule = 0, transform = TI_TRANSFORM_IDENTITY;
   double tparam = 1.0, divisor = 1.0;
   double base[ti::kMaxGroups] = {0};
-  int32_t layout = 0;   // 0 heap, 1 explicit
+  int32_t layout = 0;   // 0 heap, 1 explicit, ... 10 categorical heap (heap's fields)
   int32_t depth = 0;
   int64_t stride32 = 0, stride64 = 0;
   int32_t rows32 = 256, rows64 = 256;   // heap: rows per tile of each image (0 = HBM features)
@@ -702,7 +714,9 @@ struct ti_forest {
   std::vector<int64_t> h_node_base, h_leaf_base;
   std::vector<int32_t> h_root, h_exp_leaf_ids, h_group;
   std::vector<uint32_t> h_cat_words;   // [nwords, w0, w1, ...] per categorical node
-  int32_t has_cat = 0;
+  int32_t has_cat = 0;       // some split is categorical ...
+  int32_t has_cat_xgb = 0;   // ... with XGBoost's rule (TI_NODE_CAT_XGB)
+  int32_t has_cat_lgb = 0;   // ... with LightGBM's rule
   std::vector<unsigned char> h_leaves;   // ACC-typed
   std::vector<std::unique_ptr<DeviceForest>> devs;
 };
@@ -835,6 +849,9 @@ int validate(const ti_forest_desc* d, std::vector<int>* depth_out) {
       }
       if (d->feature[g] >= d->n_features)
         return fail(TI_ERR_INVALID, "split feature >= n_features in tree " + std::to_string(t));
+      if ((d->flags[g] & TI_NODE_CAT_XGB) && !(d->flags[g] & TI_NODE_CATEGORICAL))
+        return fail(TI_ERR_INVALID, "TI_NODE_CAT_XGB without TI_NODE_CATEGORICAL in tree " +
+                                        std::to_string(t));
       if (d->flags[g] & TI_NODE_CATEGORICAL) {
         if (!d->cat_bits || !d->cat_offset || !d->cat_nwords)
           return fail(TI_ERR_INVALID, "categorical node without cat_bits/cat_offset/cat_nwords");
@@ -900,6 +917,68 @@ void pack_heap(const ti_forest_desc* d, int D, int64_t stride, uint32_t feat_sca
         st.push_back(Item{d->left[g], 2 * it.heap + 1, it.level + 1});
         st.push_back(Item{d->right[g], 2 * it.heap + 2, it.level + 1});
       }
+    }
+  }
+}
+
+// ---------------------------------------------------- categorical heap packing
+// Layout 10 (treeinfer_cheap.h): pack_heap's record with the tree's bitsets
+// behind the leaves.  A categorical node's thr field holds the u32-word offset,
+// from the start of its tree's block, of its run [nwords, w0, w1, ...] in its
+// low 16 bits and nwords again in the next 16 (plan_cheap: a block is at most
+// kPf x 16 x R <= 64 KB).
+template <typename XT>
+int64_t cheap_block_bytes(const ti_forest_desc* d, int D, size_t acc_sz, int t) {
+  const int NI = (1 << D) - 1, NL = 1 << D;
+  int64_t words = 0;
+  for (int64_t g = d->tree_offset[t]; g < d->tree_offset[t + 1]; ++g)
+    if (d->feature[g] >= 0 && (d->flags[g] & TI_NODE_CATEGORICAL)) words += 1 + d->cat_nwords[g];
+  return static_cast<int64_t>(sizeof(HeapNode<XT>)) * NI +
+         static_cast<int64_t>(acc_sz) * NL * d->leaf_width + 4 * words;
+}
+
+template <typename XT>
+int64_t cheap_stride(const ti_forest_desc* d, int D, size_t acc_sz) {
+  int64_t m = 0;
+  for (int t = 0; t < d->n_trees; ++t) m = std::max(m, cheap_block_bytes<XT>(d, D, acc_sz, t));
+  return static_cast<int64_t>(align16(static_cast<size_t>(m)));
+}
+
+template <typename XT, typename ACC>
+void pack_cheap(const ti_forest_desc* d, int D, int64_t stride, uint32_t feat_scale,
+                std::vector<unsigned char>* img, std::vector<int32_t>* leaf_ids) {
+  using Node = HeapNode<XT>;
+  pack_heap<XT, ACC>(d, D, stride, feat_scale, img, leaf_ids);
+  const int NI = (1 << D) - 1, NL = 1 << D, LW = d->leaf_width;
+  const uint32_t words0 =
+      static_cast<uint32_t>((sizeof(Node) * NI + sizeof(ACC) * NL * LW) / sizeof(uint32_t));
+  struct Item { int32_t node; int32_t heap; };
+  std::vector<Item> st;
+  for (int t = 0; t < d->n_trees; ++t) {
+    unsigned char* rec = img->data() + static_cast<size_t>(stride) * t;
+    Node* nodes = reinterpret_cast<Node*>(rec);
+    uint32_t* words = reinterpret_cast<uint32_t*>(rec);
+    uint32_t at = words0;
+    const int64_t b = d->tree_offset[t];
+    st.assign(1, Item{0, 0});
+    while (!st.empty()) {
+      const Item it = st.back();
+      st.pop_back();
+      const int64_t g = b + it.node;
+      if (d->feature[g] < 0) continue;   // a leaf: pack_heap padded below it
+      if (d->flags[g] & TI_NODE_CATEGORICAL) {
+        const int32_t nw = d->cat_nwords[g];
+        Node nd{};
+        // low word of the thr field (little endian): run offset | nwords << 16
+        const uint32_t ref = at | (static_cast<uint32_t>(nw) << 16);
+        std::memcpy(&nd.thr, &ref, sizeof(ref));
+        nd.meta = make_cat_meta(static_cast<uint32_t>(d->feature[g]) * feat_scale, d->flags[g]);
+        nodes[it.heap] = nd;
+        words[at++] = static_cast<uint32_t>(nw);
+        for (int32_t w = 0; w < nw; ++w) words[at++] = d->cat_bits[d->cat_offset[g] + w];
+      }
+      st.push_back(Item{d->left[g], 2 * it.heap + 1});
+      st.push_back(Item{d->right[g], 2 * it.heap + 2});
     }
   }
 }
@@ -1003,7 +1082,7 @@ void pack_explicit(const ti_forest_desc* d, ti_forest* f, bool leaf_ids_only) {
         f->h_cat_words.push_back(static_cast<uint32_t>(nw));
         for (int32_t w = 0; w < nw; ++w) f->h_cat_words.push_back(d->cat_bits[d->cat_offset[g] + w]);
         std::memcpy(&e.thr, &at, sizeof(at));
-        e.meta = (static_cast<uint32_t>(d->feature[g]) & ti::kMetaFeatMask) | ti::kMetaCat;
+        e.meta = make_cat_meta(static_cast<uint32_t>(d->feature[g]), d->flags[g]);
       }
       e.left = remap[d->left[g]];
       e.right = remap[d->right[g]];
@@ -2009,7 +2088,7 @@ int upload_device(ti_forest* f, DeviceForest& d, int device) {
   TI_HIP(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
   int rc;
   if ((rc = upload(&d.tree_group, f->h_group, &d.bytes))) return rc;
-  if (f->layout == 0) {
+  if (f->layout == 0 || f->layout == 10) {
     if ((rc = upload(&d.heap32, f->h_heap32, &d.bytes))) return rc;
     if ((rc = upload(&d.heap64, f->h_heap64, &d.bytes))) return rc;
     if ((rc = upload(&d.heap_leaf_ids, f->h_heap_leaf_ids, &d.bytes))) return rc;
@@ -2219,6 +2298,35 @@ bool bheap_fixed(const ti_forest* f, int xdt, int kind) {
          bi.stride == ti::kFixTree && static_cast<uint32_t>(bi.words) * 2048u <= ti::kFixFlag;
 }
 
+// Stage size S (trees) of the heap layouts (0, 10) for tiles of R rows: as
+// many trees as keep the workgroups-per-CU count that the smallest useful
+// stage (kTilp trees) allows -- occupancy is what hides the LDS latency of the
+// walk (measured: 3 WG/CU beat 2 WG/CU by 1.7x at F = 28) -- capped by the
+// prefetch registers (kPf x 16 B x R).  `fixed`: the LDS bytes before the
+// stage (feature image + NaN flag word).  TI_HEAP_LDS_KB overrides with a
+// fixed per-workgroup budget.  0: not even one record fits.
+int64_t heap_stage_trees(const ti_forest* f, int64_t stride_b, size_t fixed, int R) {
+  const int64_t cap = static_cast<int64_t>(ti::kPf) * 16 * R / stride_b;
+  auto wgs = [&](int64_t n) { return kLdsPerCu / (fixed + static_cast<size_t>(n * stride_b)); };
+  static const int budget_kb = env_int("TI_HEAP_LDS_KB", 0);
+  int64_t S;
+  if (budget_kb > 0) {
+    const size_t b = static_cast<size_t>(budget_kb) * 1024;
+    S = b > fixed ? static_cast<int64_t>((b - fixed) / stride_b) : 0;
+    if (S >= ti::kTilp) S -= S % ti::kTilp;
+  } else {
+    S = std::min<int64_t>(ti::kTilp, cap);
+    while (S > 1 && fixed + static_cast<size_t>(S * stride_b) > kLdsPerCu) --S;
+    const size_t best = S >= 1 ? wgs(S) : 0;
+    while (S + ti::kTilp <= cap && S + ti::kTilp <= f->T && wgs(S + ti::kTilp) >= best)
+      S += ti::kTilp;
+  }
+  if (S < 1 || fixed + static_cast<size_t>(S * stride_b) > kLdsPerCu) return 0;
+  S = std::min<int64_t>(S, cap);
+  S = std::min<int64_t>(S, f->T);
+  return S;
+}
+
 int launch(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows, int32_t cols,
            int64_t stride, int kind, void* out, hipStream_t stream) {
   if (rows <= 0) return TI_OK;
@@ -2226,7 +2334,7 @@ int launch(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows, 
   // rows per tile = threads per workgroup; the heap images fixed it at create
   // time (their meta words hold [F][R] byte offsets)
   int R;
-  if (f->layout == 0) {
+  if (f->layout == 0 || f->layout == 10) {
     R = xdt == TI_F64 ? f->rows64 : f->rows32;
   } else if (f->layout == 3) {
     R = f->bh[xdt == TI_F64 ? 1 : 0].rows;
@@ -2266,39 +2374,30 @@ int launch(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows, 
   a.out = out;
 
   size_t lds = feat_bytes + 16;
-  if (f->layout == 0) {
+  if (f->layout == 0 || f->layout == 10) {
     const int64_t stride_b = xdt == TI_F64 ? f->stride64 : f->stride32;
     a.trees = xdt == TI_F64 ? d.heap64 : d.heap32;
     a.tree_stride = stride_b;
     a.heap_leaf_ids = d.heap_leaf_ids;
     a.depth = f->depth;
-    // Stage size S (trees): as many trees as keep the workgroups-per-CU count
-    // that the smallest useful stage (kTilp trees) allows -- occupancy is what
-    // hides the LDS latency of the walk (measured: 3 WG/CU beat 2 WG/CU by
-    // 1.7x at F = 28) -- capped by the prefetch registers (kPf x 16 B x R).
-    // TI_HEAP_LDS_KB overrides with a fixed per-workgroup budget.
     const size_t fixed = feat_bytes + 16;   // feature image + NaN flag word
-    const int64_t cap = static_cast<int64_t>(ti::kPf) * 16 * R / stride_b;
-    auto wgs = [&](int64_t n) { return kLdsPerCu / (fixed + static_cast<size_t>(n * stride_b)); };
-    static const int budget_kb = env_int("TI_HEAP_LDS_KB", 0);
-    int64_t S;
-    if (budget_kb > 0) {
-      const size_t b = static_cast<size_t>(budget_kb) * 1024;
-      S = b > fixed ? static_cast<int64_t>((b - fixed) / stride_b) : 0;
-      if (S >= ti::kTilp) S -= S % ti::kTilp;
-    } else {
-      S = std::min<int64_t>(ti::kTilp, cap);
-      while (S > 1 && fixed + static_cast<size_t>(S * stride_b) > kLdsPerCu) --S;
-      const size_t best = S >= 1 ? wgs(S) : 0;
-      while (S + ti::kTilp <= cap && S + ti::kTilp <= f->T && wgs(S + ti::kTilp) >= best)
-        S += ti::kTilp;
-    }
-    if (S < 1 || fixed + static_cast<size_t>(S * stride_b) > kLdsPerCu)
-      return fail(TI_ERR_UNSUPPORTED, "heap tree record does not fit in LDS");
-    S = std::min<int64_t>(S, cap);
-    S = std::min<int64_t>(S, f->T);
+    const int64_t S = heap_stage_trees(f, stride_b, fixed, R);
+    if (S < 1) return fail(TI_ERR_UNSUPPORTED, "heap tree record does not fit in LDS");
     a.stage_trees = static_cast<int32_t>(S);
     lds = fixed + static_cast<size_t>(S * stride_b);
+    if (f->layout == 10) {   // categorical heap: its own kernels, always an LDS feature image
+      if (!feat_lds) return fail(TI_ERR_UNSUPPORTED, "categorical heap needs the LDS feature image");
+      KernelFn fn = ti::kernels_cat(xdt == TI_F64, f->accum == TI_F64, f->K, f->zero_rule != 0,
+                                    f->has_cat_xgb != 0);
+      int rc = ensure_lds_attr(d.device, fn);
+      if (rc) return rc;
+      const int64_t grid = (rows + R - 1) / R;
+      if (grid > 0x7fffffff) return fail(TI_ERR_INVALID, "too many rows for one launch");
+      occ_note(fn, R, lds);
+      hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(grid)), dim3(R), lds, stream, a);
+      TI_HIP(hipGetLastError());
+      return TI_OK;
+    }
   } else if (f->layout == 3) {
     // binned heap: [bin image][flag][stage area = S tree records, also the
     // binning temp of >= 8 columns].  S as for the heap layout: the most
@@ -3246,6 +3345,44 @@ int create_chunked(const ti_forest_desc* d, const int32_t* devices, int32_t n_de
   return TI_OK;
 }
 
+// Layout 10 (treeinfer_cheap.h): whether the forest's records fit, and if so
+// the packed images (in the heap layout's fields).  The float32 view (what
+// XGBoost's DMatrix feeds) must stage at least as many trees as a lane walks
+// at once (kTilp) within the kPf x 16 x R bytes of the prefetch registers --
+// `forced` (TI_FORCE_LAYOUT=cheap) asks for one; the float64 view for one, so
+// either input type runs.  Both need their feature image in LDS, and the
+// categorical nodes one rule (the kernel is compiled per rule).
+bool plan_cheap(const ti_forest_desc* desc, ti_forest* f, int D, bool forced) {
+  if (f->has_cat_xgb && f->has_cat_lgb) return false;
+  const size_t acc_sz = f->accum == TI_F64 ? 8 : 4;
+  const int want_rows = env_int("TI_HEAP_ROWS", 0);
+  const int r32 = pick_rows(f->F, 4, want_rows), r64 = pick_rows(f->F, 8, want_rows);
+  if (r32 <= 0 || r64 <= 0 || r32 > 512 || r64 > 512) return false;
+  if (static_cast<size_t>(f->F) * r32 * 4 > kFeatLdsMax || static_cast<size_t>(f->F) * r64 * 8 > kFeatLdsMax)
+    return false;
+  const uint32_t sc32 = static_cast<uint32_t>(r32) * 4u, sc64 = static_cast<uint32_t>(r64) * 8u;
+  if (static_cast<uint64_t>(f->F) * std::max(sc32, sc64) > ti::kMetaFeatMask) return false;
+  const int64_t s32 = cheap_stride<float>(desc, D, acc_sz), s64 = cheap_stride<double>(desc, D, acc_sz);
+  const int64_t cap32 = static_cast<int64_t>(ti::kPf) * 16 * r32 / s32;
+  if (cap32 < (forced ? 1 : ti::kTilp)) return false;
+  const size_t fixed32 = align16(static_cast<size_t>(f->F) * r32 * 4) + 16;
+  const size_t fixed64 = align16(static_cast<size_t>(f->F) * r64 * 8) + 16;
+  if (heap_stage_trees(f, s32, fixed32, r32) < 1 || heap_stage_trees(f, s64, fixed64, r64) < 1)
+    return false;
+  f->rows32 = r32;
+  f->rows64 = r64;
+  f->stride32 = s32;
+  f->stride64 = s64;
+  if (f->accum == TI_F64) {
+    pack_cheap<float, double>(desc, D, s32, sc32, &f->h_heap32, &f->h_heap_leaf_ids);
+    pack_cheap<double, double>(desc, D, s64, sc64, &f->h_heap64, nullptr);
+  } else {
+    pack_cheap<float, float>(desc, D, s32, sc32, &f->h_heap32, &f->h_heap_leaf_ids);
+    pack_cheap<double, float>(desc, D, s64, sc64, &f->h_heap64, nullptr);
+  }
+  return true;
+}
+
 // The forest whose DeviceForest (stream, staging buffers, lock) serves a slot.
 ti_forest* base_forest(ti_forest* f) {
   while (!f->parts.empty()) f = f->parts[0].get();
@@ -3297,7 +3434,11 @@ int ti_forest_create(const ti_forest_desc* desc, const int32_t* devices, int32_t
   for (int k = 0; k < f->K; ++k) f->base[k] = desc->base_margin[k];
   for (int64_t i = 0; i < desc->n_nodes; ++i)
     if (desc->feature[i] >= 0) {
-      if (desc->flags[i] & TI_NODE_CATEGORICAL) f->has_cat = 1;
+      if (desc->flags[i] & TI_NODE_CATEGORICAL) {
+        f->has_cat = 1;
+        if (desc->flags[i] & TI_NODE_CAT_XGB) f->has_cat_xgb = 1;
+        else f->has_cat_lgb = 1;
+      }
       else if (desc->flags[i] & TI_NODE_ZERO_FLIP) f->zero_rule = 1;
     }
   f->h_group.assign(f->T, 0);
@@ -3308,9 +3449,12 @@ int ti_forest_create(const ti_forest_desc* desc, const int32_t* devices, int32_t
   const size_t acc_sz = f->accum == TI_F64 ? 8 : 4;
   const int D = f->depth;
   // layout: binned heap for depth <= 8, the record layouts (6-9) for deeper
-  // trees, the float explicit kernel for categorical splits;
-  // TI_FORCE_LAYOUT=heap|explicit|rexplicit|lexplicit|hexplicit|texplicit
-  // overrides (tests run every layout on the same forest)
+  // trees; categorical splits: the categorical heap (10) for XGBoost-rule
+  // forests of depth <= 8 whose records fit a stage (plan_cheap), the float
+  // explicit kernel (1) otherwise and for every LightGBM-rule forest;
+  // TI_FORCE_LAYOUT=heap|explicit|rexplicit|lexplicit|hexplicit|texplicit|cheap
+  // overrides (tests run every layout on the same forest); cheap puts any
+  // categorical forest of depth <= 8 on layout 10, whichever rule it uses
   const char* force = env_knob("TI_FORCE_LAYOUT");
   std::string want = force ? force : "";
   bool use_heap = D <= kMaxHeapDepth;
@@ -3318,8 +3462,12 @@ int ti_forest_create(const ti_forest_desc* desc, const int32_t* devices, int32_t
   if (want == "explicit" || want == "rexplicit" || want == "lexplicit" || want == "hexplicit" ||
       want == "texplicit")
     use_heap = false;
-  // categorical splits are evaluated by the explicit kernel only
+  // categorical splits are evaluated by the explicit kernel and the categorical heap
   if (f->has_cat) use_heap = false;
+  bool use_cheap = false;
+  if (f->has_cat && D >= 1 && D <= kMaxHeapDepth &&
+      (want == "cheap" || (f->has_cat_xgb && want.empty())))
+    use_cheap = plan_cheap(desc, f.get(), D, want == "cheap");
   // binned heap (rank-binned features, 4-byte nodes) for complete-able trees
   // without LightGBM zero-missing or categorical splits; TI_FORCE_LAYOUT=heap
   // keeps the float-compare heap kernel
@@ -3337,7 +3485,9 @@ int ti_forest_create(const ti_forest_desc* desc, const int32_t* devices, int32_t
       for (auto& bi : f->bh) bi = ti_forest::BinImage();
     }
   }
-  if (use_bheap) {
+  if (use_cheap) {
+    f->layout = 10;   // packed by plan_cheap
+  } else if (use_bheap) {
     f->layout = 3;
   } else if (use_heap) {
     const int NI = (1 << D) - 1, NL = 1 << D;
@@ -3485,7 +3635,9 @@ int ti_forest_get_info(const ti_forest* f, ti_forest_info* info) {
   } else {
     for (auto& p : f->parts) info->device_bytes += p->devs.empty() ? 0 : p->devs[0]->bytes;
   }
-  info->tree_stride_bytes = f->layout == 0 ? f->stride32 : f->layout == 3 ? f->bh[0].stride : 0;
+  const ti_forest* pf = f->parts.empty() ? f : f->parts[0].get();   // a chunked forest: its first part
+  info->tree_stride_bytes = f->layout == 0 ? f->stride32 : f->layout == 3 ? f->bh[0].stride
+                            : f->layout == 10 ? pf->stride32 : 0;
   // walk id: the kernel variant a PMC pass was taken on (bench.py matches it)
   info->walk = bheap_fixed(f, TI_F32, TI_OUTPUT_PREDICT) ? (TI_FIX_SROOT ? 2 : 1) : 0;
   info->bin_bits = f->layout == 3 ? (f->bh[0].b16 ? 16 : 8)
@@ -3494,6 +3646,11 @@ int ti_forest_get_info(const ti_forest* f, ti_forest_info* info) {
                    : (f->layout == 7 || f->layout == 9) ? f->lx_ilp : 0;
   info->n_stages = (f->layout == 7 || f->layout == 9) && !f->h_lx_stage.empty()
                        ? static_cast<int32_t>(f->h_lx_stage.size() - 1) : 0;
+  if (f->layout == 10) {   // the stages of a float32 batch (launch sizes them the same way)
+    const size_t fixed = align16(static_cast<size_t>(pf->F) * pf->rows32 * 4) + 16;
+    const int64_t S = heap_stage_trees(pf, pf->stride32, fixed, pf->rows32);
+    info->n_stages = S > 0 ? static_cast<int32_t>((pf->T + S - 1) / S) : 0;
+  }
   info->top_depth = (f->layout == 8 || f->layout == 9) ? f->hx_top : 0;
   info->bottom = f->layout == 9 ? f->tx8 : 0;
   // the TreeSHAP coefficient table of slot 0 (of the first part)

@@ -13,7 +13,9 @@ using KernelFn = void (*)(KArgs);
 // record explicit, 8 heap top + record bottom, 9 heap top + staged record
 // bottom (2, 4 and 5 were retired in round 3); 10 selects the fixed-layout
 // walk of layout 3 (bheap_fix_kernel), 11 layout 9's compact u8 bottom, 12
-// its compact u16 bottom, 13 the u16 bottom walked two lanes a row.
+// its compact u16 bottom, 13 the u16 bottom walked two lanes a row.  (These
+// ids are this header's own: the public layout 10 of ti_forest_info, the
+// categorical heap, has its kernels and selection in treeinfer_cheap.h.)
 // fl: feature image in
 // LDS; z: LightGBM zero rule; b16 / pf: binned heap (and layout 9) bin width
 // and prefetch depth.

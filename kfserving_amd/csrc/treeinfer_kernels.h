@@ -54,7 +54,8 @@ namespace ti {
 
 constexpr uint32_t kMetaNanLeft = 0x80000000u;
 constexpr uint32_t kMetaZeroFlip = 0x40000000u;
-constexpr uint32_t kMetaCat = 0x20000000u;        // explicit layout: categorical node
+constexpr uint32_t kMetaCat = 0x20000000u;        // layouts 1 and 10: categorical node
+constexpr uint32_t kMetaCatXgb = 0x10000000u;     // ... that takes XGBoost's rule (cat_left_xgb)
 constexpr uint32_t kMetaFeatMask = 0x00FFFFFFu;
 constexpr int kMaxGroups = 16;
 constexpr int kExpIlp = TI_EXP_ILP;       // trees per lane in the global explicit kernels
@@ -167,6 +168,19 @@ __device__ __forceinline__ bool cat_left(const uint32_t* bs, double x) {
   const uint32_t w = v >> 5;
   if (w >= bs[0]) return false;
   return (bs[1 + w] >> (v & 31u)) & 1u;
+}
+
+// XGBoost's categorical rule (xgboost >= 1.7 common::Decision / GetNextNode):
+// a NaN takes the node's default child (meta bit 31); x < 0 or x >= 2^24 is
+// an invalid category and goes left (-0.0 is category 0); otherwise the
+// category trunc(x) goes RIGHT iff it is inside the node's bitset and set.
+__device__ __forceinline__ bool cat_left_xgb(const uint32_t* bs, double x, uint32_t meta) {
+  if (x != x) return (int32_t)meta < 0;
+  if (!(x >= 0.0 && x < 16777216.0)) return true;
+  const uint32_t v = static_cast<uint32_t>(x);
+  const uint32_t w = v >> 5;
+  if (w >= bs[0]) return true;
+  return ((bs[1 + w] >> (v & 31u)) & 1u) == 0u;
 }
 
 // One heap node from LDS in a single wide read (ds_read_b64 / ds_read_b128).
@@ -1087,7 +1101,8 @@ __global__ void __launch_bounds__(512) explicit_predict_kernel(const KArgs a) {
         }
         bool l = go_left<ZERO>(x, thr[q], nd[q].y);
         if (a.cat_words != nullptr && (nd[q].y & kMetaCat))   // uniform test, then rare branch
-          l = cat_left(a.cat_words + nd[q].x, (double)x);
+          l = (nd[q].y & kMetaCatXgb) ? cat_left_xgb(a.cat_words + nd[q].x, (double)x, nd[q].y)
+                                      : cat_left(a.cat_words + nd[q].x, (double)x);
         const int32_t next = l ? (int32_t)nd[q].z : (int32_t)nd[q].w;
         c[q] = c[q] < 0 ? c[q] : next;
         active |= c[q] >= 0;

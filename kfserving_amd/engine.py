@@ -21,7 +21,7 @@ import numpy as np
 from .forest import (Forest, OUT_CONTRIB, OUT_LEAF, OUT_MARGIN, OUT_PREDICT, TI_F32, TI_F64,
                      TI_I32)
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 _LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("TREEINFER_LIB", os.path.join(_LIB_DIR, "libtreeinfer.so"))
 

@@ -27,6 +27,7 @@ TI_I32 = 2
 NODE_NAN_LEFT = 0x01
 NODE_ZERO_FLIP = 0x02
 NODE_CATEGORICAL = 0x04
+NODE_CAT_XGB = 0x08      # with NODE_CATEGORICAL: XGBoost's rule (in set -> right)
 
 # transforms
 T_IDENTITY = 0
@@ -84,8 +85,9 @@ class Forest:
     transform: int = T_IDENTITY
     transform_param: float = 1.0
     input_dtype: int = TI_F32        # how the plugin feeds X (xgb/sk: f32, lgb: f64)
-    # categorical splits (LightGBM): node goes left iff bit trunc(x) is set in
-    # cat_bits[cat_offset[n] : cat_offset[n] + cat_nwords[n]]
+    # categorical splits: LightGBM nodes go left iff bit trunc(x) is set in
+    # cat_bits[cat_offset[n] : cat_offset[n] + cat_nwords[n]]; XGBoost nodes
+    # (NODE_CAT_XGB) go right iff it is set (include/treeinfer.h)
     cat_bits: Optional[np.ndarray] = None       # uint32 [W]
     cat_offset: Optional[np.ndarray] = None     # int64 [N]
     cat_nwords: Optional[np.ndarray] = None     # int32 [N]
@@ -154,6 +156,8 @@ class Forest:
         if self.cover is not None and self.cover.shape[0] != N:
             raise ValueError("cover must be [n_nodes]")
         cat = internal & ((self.flags & NODE_CATEGORICAL) != 0)
+        if np.any(internal & ((self.flags & NODE_CAT_XGB) != 0) & ~cat):
+            raise ValueError("NODE_CAT_XGB without NODE_CATEGORICAL")
         if cat.any():
             if self.cat_bits is None or self.cat_offset is None or self.cat_nwords is None:
                 raise ValueError("categorical nodes without bitsets")

@@ -15,6 +15,12 @@ Predict semantics encoded (upstream xgboost 0.82 ``RegTree::GetNext`` /
 ``CPUPredictor::PredValue``): go left iff ``x < split`` in float32, a missing
 value takes the node's default child, leaves summed in float32 in tree order
 per output group from 0 and then added to the base margin.
+
+Categorical nodes of JSON / UBJSON models (``split_type == 1``, xgboost >= 1.7
+``common::Decision`` / ``GetNextNode``): a missing value takes the default
+child; a value below 0 or at or above 2^24 is an invalid category and goes
+left; otherwise the value truncated to an integer goes right iff it is in the
+node's category set (include/treeinfer.h, TI_NODE_CAT_XGB).
 """
 from __future__ import annotations
 
@@ -25,8 +31,11 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
-from ..forest import (Forest, NODE_NAN_LEFT, TI_F32, T_ARGMAX, T_EXP, T_HINGE, T_IDENTITY,
-                      T_SIGMOID, T_SOFTMAX, concat_trees)
+from ..forest import (Forest, NODE_CAT_XGB, NODE_CATEGORICAL, NODE_NAN_LEFT, TI_F32, T_ARGMAX,
+                      T_EXP, T_HINGE, T_IDENTITY, T_SIGMOID, T_SOFTMAX, concat_trees)
+
+MAX_CATEGORY = 1 << 24      # xgboost's kMaxCat: category codes are in [0, 2^24)
+_CAT_MIN_VERSION = (1, 7, 0)   # 1.5 / 1.6 sent invalid categories to the default child
 
 # on-disk structs of the legacy / binf binary (little endian)
 _LEARNER_PARAM = 136       # LearnerModelParam
@@ -133,15 +142,82 @@ def _tree_from_arrays(cleft, cright, sindex, value, deleted=None, sum_hess=None)
     }
 
 
+def _category_codes(codes) -> np.ndarray:
+    """One node's category set as validated int64 codes in [0, 2^24)."""
+    try:
+        raw = np.asarray(codes, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError) as e:
+        raise XGBoostFormatError(f"malformed category set: {e}") from e
+    if raw.size and not (np.all(np.isfinite(raw)) and np.all(raw == np.floor(raw))):
+        raise XGBoostFormatError("category codes must be integers")
+    if raw.size and (raw.min() < 0 or raw.max() >= MAX_CATEGORY):
+        raise XGBoostFormatError(f"category code outside [0, {MAX_CATEGORY})")
+    return raw.astype(np.int64)
+
+
+def _set_categorical(t: dict, cats) -> None:
+    """Make the nodes ``cats`` names (node id -> category codes) of canonical
+    tree ``t`` XGBoost-rule categorical nodes: threshold unused (0), the
+    default child kept in NAN_LEFT, one bitset per node just long enough for
+    its highest category."""
+    n = t["feature"].shape[0]
+    off = np.full(n, -1, dtype=np.int64)
+    nw = np.zeros(n, dtype=np.int32)
+    words, total = [], 0
+    cats = {int(k): v for k, v in cats.items()}
+    for node in sorted(cats):
+        if not (0 <= node < n) or t["feature"][node] < 0:
+            raise XGBoostFormatError(f"categorical node {node} is not a split node")
+        codes = _category_codes(cats[node])
+        bits = np.zeros(int(codes.max()) // 32 + 1 if codes.size else 0, dtype=np.uint32)
+        np.bitwise_or.at(bits, codes // 32, np.uint32(1) << (codes % 32).astype(np.uint32))
+        off[node], nw[node] = total, bits.size
+        words.append(bits)
+        total += bits.size
+        t["threshold"][node] = 0.0
+        t["flags"][node] = NODE_CATEGORICAL | NODE_CAT_XGB | (int(t["flags"][node]) & NODE_NAN_LEFT)
+    t["cat_offset"], t["cat_nwords"] = off, nw
+    t["cat_words"] = np.concatenate(words) if words else np.zeros(0, dtype=np.uint32)
+
+
+def _concat_categories(trees: List[dict]):
+    """cat_bits / cat_offset / cat_nwords of the forest from the per-tree
+    bitsets (node offsets become offsets into the forest's words)."""
+    if not any("cat_words" in t for t in trees):
+        return None, None, None
+    base, words, offs, nws = 0, [], [], []
+    for t in trees:
+        n = t["feature"].shape[0]
+        o = t.get("cat_offset", np.full(n, -1, dtype=np.int64)).copy()
+        o[o >= 0] += base
+        offs.append(o)
+        nws.append(t.get("cat_nwords", np.zeros(n, dtype=np.int32)))
+        w = t.get("cat_words", np.zeros(0, dtype=np.uint32))
+        words.append(w)
+        base += w.size
+    bits = np.concatenate(words).astype(np.uint32)
+    if bits.size == 0:          # only empty sets: the ABI still wants a words array
+        bits = np.zeros(1, dtype=np.uint32)
+    return bits, np.concatenate(offs), np.concatenate(nws).astype(np.int32)
+
+
 def _assemble(trees: List[dict], tree_info: np.ndarray, num_feature: int, num_group: int,
-              base_score: float, objective: str, base_is_margin: bool, base_first: bool,
+              base_score, objective: str, base_is_margin: bool, base_first: bool,
               version: Tuple[int, int, int], feature_names=None, fmt: str = "") -> Forest:
+    """``base_score``: one value, or one per output group (xgboost >= 2 vector)."""
     cat = concat_trees(trees, 1)
+    cat_bits, cat_offset, cat_nwords = _concat_categories(trees)
     used = cat["feature"][cat["feature"] >= 0]
     n_features = max(int(num_feature), int(used.max()) + 1 if used.size else 1)
     K = max(1, int(num_group))
-    margin = base_score if base_is_margin else prob_to_margin(objective, base_score)
-    base = np.full(K, float(np.float32(margin)), dtype=np.float64)
+    scores = np.atleast_1d(np.asarray(base_score, dtype=np.float64))
+    margins = [s if base_is_margin else prob_to_margin(objective, s) for s in scores]
+    base = np.empty(K, dtype=np.float64)
+    base[:] = [float(np.float32(m)) for m in margins]     # one value broadcasts over K
+    if scores.size == 1:
+        base_score = float(scores[0])
+    else:
+        base_score = [float(s) for s in scores]
     tinfo = np.asarray(tree_info, dtype=np.int32)
     if tinfo.shape[0] != len(trees):
         raise XGBoostFormatError("tree_info length does not match the number of trees")
@@ -156,6 +232,7 @@ def _assemble(trees: List[dict], tree_info: np.ndarray, num_feature: int, num_gr
         input_dtype=TI_F32, library="xgboost", objective=objective,
         feature_names=feature_names,
         meta={"format": fmt, "version": version, "base_score": base_score},
+        cat_bits=cat_bits, cat_offset=cat_offset, cat_nwords=cat_nwords,
     ).contiguous()
 
 
@@ -219,11 +296,75 @@ def _json_num(v) -> float:
     return float(v)
 
 
+def _json_base_score(v, num_class: int):
+    """learner_model_param.base_score: a number (or its string), or the
+    bracketed list recent xgboost writes (``"[5E-1]"``, or one value per
+    class): one value, or exactly ``num_class`` of them."""
+    if isinstance(v, str) and v.strip().startswith("["):
+        body = v.strip()
+        if not body.endswith("]"):
+            raise XGBoostFormatError(f"malformed base_score {v!r}")
+        try:
+            vals = [float(p) for p in body[1:-1].split(",")]
+        except ValueError as e:
+            raise XGBoostFormatError(f"malformed base_score {v!r}") from e
+        if len(vals) != 1 and len(vals) != max(1, num_class):
+            raise XGBoostFormatError(f"base_score holds {len(vals)} values, expected 1 or "
+                                     f"num_class = {max(1, num_class)}")
+        return vals[0] if len(vals) == 1 else vals
+    try:
+        return _json_num(v)
+    except (TypeError, ValueError) as e:
+        raise XGBoostFormatError(f"malformed base_score {v!r}") from e
+
+
+def _int_array(jt: dict, key: str) -> np.ndarray:
+    try:
+        a = np.asarray(jt.get(key, []), dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError) as e:
+        raise XGBoostFormatError(f"malformed {key}: {e}") from e
+    if a.size and not (np.all(np.isfinite(a)) and np.all(a == np.floor(a))):
+        raise XGBoostFormatError(f"{key} must hold integers")
+    return a.astype(np.int64)
+
+
+def _json_categories(jt: dict, n_nodes: int, version) -> dict:
+    """The categorical nodes of one JSON tree as {node id: category codes},
+    from split_type / categories / categories_nodes / categories_segments /
+    categories_sizes; every inconsistency is an XGBoostFormatError."""
+    split_type = _int_array(jt, "split_type")
+    nodes = _int_array(jt, "categories_nodes")
+    if not split_type.any() and nodes.size == 0:
+        return {}
+    if tuple(version) < _CAT_MIN_VERSION:
+        raise XGBoostFormatError(
+            "categorical splits of xgboost version %s are not supported (invalid categories "
+            "took the default child before 1.7.0)" % ".".join(str(v) for v in version))
+    if split_type.size != n_nodes:
+        raise XGBoostFormatError("split_type length does not match the number of nodes")
+    if np.any((split_type != 0) & (split_type != 1)):
+        raise XGBoostFormatError("unknown split_type")
+    segments = _int_array(jt, "categories_segments")
+    sizes = _int_array(jt, "categories_sizes")
+    categories = _int_array(jt, "categories")
+    if segments.size != nodes.size or sizes.size != nodes.size:
+        raise XGBoostFormatError("categories_nodes / _segments / _sizes differ in length")
+    if nodes.size and (nodes.min() < 0 or nodes.max() >= n_nodes or np.any(np.diff(nodes) <= 0)):
+        raise XGBoostFormatError("categories_nodes must be strictly increasing node ids")
+    named = np.zeros(n_nodes, dtype=bool)
+    named[nodes] = True
+    if np.any(named != (split_type == 1)):
+        raise XGBoostFormatError("categories_nodes does not name exactly the split_type == 1 nodes")
+    if np.any(segments < 0) or np.any(sizes < 0) or np.any(segments + sizes > categories.size):
+        raise XGBoostFormatError("category segment outside the categories array")
+    return {int(nd): categories[b:b + s] for nd, b, s in zip(nodes, segments, sizes)}
+
+
 def _parse_json(doc: dict) -> Forest:
     learner = doc["learner"]
     lmp = learner["learner_model_param"]
-    base_score = _json_num(lmp.get("base_score", 0.5))
     num_class = int(_json_num(lmp.get("num_class", 0)))
+    base_score = _json_base_score(lmp.get("base_score", 0.5), num_class)
     num_feature = int(_json_num(lmp.get("num_feature", 0)))
     objective = learner["objective"]["name"]
     gb = learner["gradient_booster"]
@@ -236,20 +377,21 @@ def _parse_json(doc: dict) -> Forest:
         weights = np.asarray(gb["weight_drop"], dtype=np.float32)
     else:
         raise XGBoostFormatError(f"booster '{name}' is not a tree ensemble")
+    version = tuple(int(v) for v in doc.get("version", [1, 0, 0]))
     trees = []
     for i, jt in enumerate(model["trees"]):
-        if any(int(s) != 0 for s in jt.get("split_type", [])):
-            raise XGBoostFormatError("categorical splits are not supported yet")
         cleft = np.asarray(jt["left_children"], dtype=np.int32)
         dl = np.asarray(jt["default_left"], dtype=np.uint32) & 1
         sindex = np.asarray(jt["split_indices"], dtype=np.uint32) | (dl << 31)
         t = _tree_from_arrays(cleft, jt["right_children"], sindex, jt["split_conditions"],
                               sum_hess=jt.get("sum_hessian"))
+        cats = _json_categories(jt, cleft.shape[0], version)
+        if cats:
+            _set_categorical(t, cats)
         if weights is not None:
             lv = t["leaf_value"][:, 0].astype(np.float32) * weights[i]
             t["leaf_value"] = lv.astype(np.float64).reshape(-1, 1)
         trees.append(t)
-    version = tuple(int(v) for v in doc.get("version", [1, 0, 0]))
     K = max(1, num_class)
     names = learner.get("feature_names") or None
     return _assemble(trees, model["tree_info"], num_feature, K, base_score, objective,
@@ -338,12 +480,29 @@ def write_legacy_binary(path: str, trees: List[dict], tree_info, num_feature: in
 def json_model_doc(trees: List[dict], tree_info, num_feature: int, num_class: int,
                    base_score: float, objective: str, version=(1, 3, 0), arrays=False) -> dict:
     """The xgboost >= 1.0 JSON model document (subset the loader reads);
-    ``arrays=True`` keeps numpy arrays (for the UBJSON writer)."""
+    ``arrays=True`` keeps numpy arrays (for the UBJSON writer).  A tree may
+    carry ``cats``, a mapping of node id to category codes: those nodes are
+    written as categorical splits (split_type 1 and the four categories_*
+    arrays of xgboost >= 1.5; the loader takes them from version 1.7.0 on)."""
     jt = []
     for i, t in enumerate(trees):
         n = len(t["cleft"])
         conv = (lambda a, dt: np.asarray(a, dtype=dt)) if arrays else \
             (lambda a, dt: [dt(v).item() for v in np.asarray(a, dtype=dt)])
+        extra = {}
+        if t.get("cats"):
+            cats = {int(k): np.asarray(v, dtype=np.int64).reshape(-1) for k, v in t["cats"].items()}
+            nodes = sorted(cats)
+            sizes = [cats[k].size for k in nodes]
+            split_type = np.zeros(n, dtype=np.uint8)
+            split_type[nodes] = 1
+            extra = {
+                "split_type": conv(split_type, np.uint8),
+                "categories": conv(np.concatenate([cats[k] for k in nodes]), np.int32),
+                "categories_nodes": conv(nodes, np.int32),
+                "categories_segments": conv(np.cumsum([0] + sizes[:-1]), np.int64),
+                "categories_sizes": conv(sizes, np.int64),
+            }
         jt.append({
             "id": i,
             "left_children": conv(t["cleft"], np.int32),
@@ -354,6 +513,7 @@ def json_model_doc(trees: List[dict], tree_info, num_feature: int, num_class: in
             "sum_hessian": conv(t.get("sum_hess", np.zeros(n)), np.float32),
             "tree_param": {"num_nodes": str(n), "num_feature": str(num_feature),
                            "size_leaf_vector": "0"},
+            **extra,
         })
     return {
         "version": list(version),
@@ -448,11 +608,39 @@ def synthetic_complete_trees(n_trees: int, depth: int, n_features: int, seed: in
     return trees, tree_info
 
 
+def add_categorical_splits(trees: List[dict], cat_features, n_categories: int, seed: int,
+                           frac: float = 0.5) -> List[dict]:
+    """Turn a seeded fraction of the splits on ``cat_features`` of XGBoost raw
+    trees into categorical nodes (``cats``: node id -> category codes) with
+    random non-empty sets over ``n_categories`` values; the sibling of
+    lightgbm_format.add_categorical_splits.  The nodes keep their feature,
+    children and default direction; their split condition is unused."""
+    rng = np.random.default_rng(seed)
+    cat_features = np.asarray(cat_features, dtype=np.int64)
+    for t in trees:
+        cleft = np.asarray(t["cleft"])
+        feat = (np.asarray(t["sindex"], dtype=np.uint32) & 0x7FFFFFFF).astype(np.int64)
+        cats = dict(t.get("cats") or {})
+        for i in np.nonzero((cleft != -1) & np.isin(feat, cat_features))[0]:
+            if rng.random() >= frac:
+                continue
+            members = np.nonzero(rng.random(n_categories) < 0.4)[0]
+            if members.size == 0:
+                members = np.array([int(rng.integers(0, n_categories))])
+            cats[int(i)] = members.astype(np.int32)
+        if cats:
+            t["cats"] = cats
+    return trees
+
+
 def forest_from_raw_trees(trees: List[dict], tree_info, num_feature: int, num_class: int,
                           base_score: float, objective: str, legacy: bool = True) -> Forest:
     """Canonical forest straight from RegTree arrays (what the writers store)."""
     canon = [_tree_from_arrays(t["cleft"], t["cright"], t["sindex"], t["value"],
                               sum_hess=t.get("sum_hess")) for t in trees]
+    for c, t in zip(canon, trees):
+        if t.get("cats"):
+            _set_categorical(c, t["cats"])
     return _assemble(canon, tree_info, num_feature, max(1, num_class), base_score, objective,
                      base_is_margin=legacy, base_first=False,
                      version=(0, 82, 0) if legacy else (1, 3, 0), fmt="raw")

@@ -114,6 +114,9 @@ def xgb_matrix_from_list(instances) -> np.ndarray:
     stored (missing -> default child) while NaN is stored as a value, which never
     satisfies ``x < split`` (always the right child).  Encoded for the canonical
     kernel as 0 -> NaN (missing) and NaN -> +inf (right at every split).
+
+    Not for models with categorical splits (xgboost >= 1.7): category 0 would
+    be unreachable; XGBoostModel.request_matrix casts their lists plainly.
     """
     X = np.asarray(instances, dtype=np.float64)
     if X.ndim == 1:

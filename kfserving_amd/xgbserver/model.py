@@ -40,7 +40,16 @@ class XGBoostModel(GPUForestMixin, KFModel):
         instances = request["instances"]
         if isinstance(instances, np.ndarray) and not isinstance(instances, JsonInstances):
             return self.tensor_matrix(instances)  # DMatrix(ndarray): NaN = missing
+        if self._list_is_plain():
+            # a model with categorical splits comes from xgboost >= 1.7, whose
+            # DMatrix(list) is the plain float32 cast with NaN = missing (under
+            # the 0.82 rule category 0 could never be reached)
+            return self.tensor_matrix(np.asarray(instances, dtype=np.float64))
         return xgb_matrix_from_list(instances)    # DMatrix(list) semantics (JSON rows)
+
+    def _list_is_plain(self) -> bool:
+        f = self._forest
+        return f is not None and f.has_categorical
 
     def tensor_matrix(self, X: np.ndarray) -> np.ndarray:
         # DMatrix(ndarray) stores float32: a float64 array is rounded first
@@ -52,8 +61,12 @@ class XGBoostModel(GPUForestMixin, KFModel):
         return X if X.dtype == np.float32 else X.astype(np.float32)
 
     # the native HTTP front end answers batched v1 :predict bodies of this
-    # model itself, with DMatrix(list)'s element rule (kfbatch.h KB_IN_XGB_LIST)
-    native_v1_transform = 1
+    # model itself, with DMatrix(list)'s element rule (kfbatch.h KB_IN_XGB_LIST);
+    # a model with categorical splits takes the plain float32 cast (request_matrix)
+    @property
+    def native_v1_transform(self):
+        return 0 if self._list_is_plain() else 1
+
     # ... and its V2 tensor requests (FP32 / FP64 JSON data, kh_add_v2_tensor_predict):
     # tensor_matrix is the plain float32 cast the native batcher applies
     native_v2_transform = 0
@@ -63,7 +76,8 @@ class XGBoostModel(GPUForestMixin, KFModel):
         # right) and the float32 cast are applied by the native batcher while
         # it copies the rows (KB_IN_XGB_LIST), the conversion
         # xgb_matrix_from_list makes in numpy
-        if kind == "instances" and isinstance(chunk, JsonInstances) and chunk.ndim == 2:
+        if (kind == "instances" and isinstance(chunk, JsonInstances) and chunk.ndim == 2
+                and not self._list_is_plain()):
             return np.asarray(chunk), 1
         return super().native_request(chunk, kind)
 
