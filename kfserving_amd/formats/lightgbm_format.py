@@ -269,15 +269,24 @@ def write_lightgbm_text(path: str, trees: List[dict], n_features: int, objective
 
 
 def add_categorical_splits(trees: List[dict], cat_features, n_categories: int, seed: int,
-                           frac: float = 0.5) -> List[dict]:
+                           frac: float = 0.5, edge_frac: float = 0.0,
+                           root_trees: int = 0) -> List[dict]:
     """Turn a fraction of the splits on ``cat_features`` into categorical
     splits (decision_type bit 0, threshold = index into cat_boundaries) with
     random bitsets over ``n_categories`` values -- the shape lightgbm 2.3.1
     writes (Tree::SplitCategorical): each bitset is just long enough for its
-    highest category."""
+    highest category.
+
+    ``edge_frac`` and ``root_trees`` are those of
+    xgboost_format.add_categorical_splits (sets at the edges of a bitset, and
+    categorical roots in the first trees); off, the output is unchanged."""
+    from .xgboost_format import edge_category_sets
     rng = np.random.default_rng(seed)
+    erng = np.random.default_rng([seed, 24])
+    edge = edge_category_sets(n_categories)
+    n_edge = 0
     cat_features = np.asarray(cat_features)
-    for t in trees:
+    for ti, t in enumerate(trees):
         if len(t["leaf_value"]) <= 1:
             continue
         feat = np.asarray(t["split_feature"]).copy()
@@ -285,12 +294,19 @@ def add_categorical_splits(trees: List[dict], cat_features, n_categories: int, s
         dt = np.asarray(t["decision_type"]).copy()
         bounds, words = [0], []
         for i in range(feat.shape[0]):
-            if rng.random() >= frac:
+            root = i == 0 and ti < root_trees
+            if rng.random() >= frac and not root:
                 continue
             feat[i] = cat_features[rng.integers(0, cat_features.shape[0])]
             members = np.nonzero(rng.random(n_categories) < 0.4)[0]
             if members.size == 0:
                 members = np.array([int(rng.integers(0, n_categories))])
+            if root:
+                feat[i] = cat_features[ti % cat_features.shape[0]]
+                members = edge[ti % len(edge)]
+            elif edge_frac > 0 and erng.random() < edge_frac:
+                members = edge[n_edge % len(edge)]
+                n_edge += 1
             nw = int(members.max()) // 32 + 1
             bits = np.zeros(nw, dtype=np.uint64)
             for m in members:

@@ -608,16 +608,38 @@ def synthetic_complete_trees(n_trees: int, depth: int, n_features: int, seed: in
     return trees, tree_info
 
 
+def edge_category_sets(n_categories: int) -> List[np.ndarray]:
+    """The category sets at the edges of a bitset over ``n_categories`` values
+    (its last word is word (n - 1) // 32): only bit 31 of the last word, every
+    category, only bit 0 of the last word, {n - 1} and {0}."""
+    n = int(n_categories)
+    last = 32 * ((n - 1) // 32)
+    return [np.array([last + 31], dtype=np.int32), np.arange(n, dtype=np.int32),
+            np.array([last], dtype=np.int32), np.array([n - 1], dtype=np.int32),
+            np.array([0], dtype=np.int32)]
+
+
 def add_categorical_splits(trees: List[dict], cat_features, n_categories: int, seed: int,
-                           frac: float = 0.5) -> List[dict]:
+                           frac: float = 0.5, edge_frac: float = 0.0,
+                           root_trees: int = 0) -> List[dict]:
     """Turn a seeded fraction of the splits on ``cat_features`` of XGBoost raw
     trees into categorical nodes (``cats``: node id -> category codes) with
     random non-empty sets over ``n_categories`` values; the sibling of
     lightgbm_format.add_categorical_splits.  The nodes keep their feature,
-    children and default direction; their split condition is unused."""
+    children and default direction; their split condition is unused.
+
+    For tests of the bitset edges (both default to off, and draw from a stream
+    of their own, so the plain output is the same with or without them):
+    ``edge_frac`` of the categorical nodes take one of edge_category_sets in
+    turn instead of their random set, and the roots of the first
+    ``root_trees`` trees become categorical nodes on ``cat_features[i % n]``
+    with edge set ``i % 5`` (tree i), so every row meets a categorical node."""
     rng = np.random.default_rng(seed)
+    erng = np.random.default_rng([seed, 24])
+    edge = edge_category_sets(n_categories)
+    n_edge = 0
     cat_features = np.asarray(cat_features, dtype=np.int64)
-    for t in trees:
+    for ti, t in enumerate(trees):
         cleft = np.asarray(t["cleft"])
         feat = (np.asarray(t["sindex"], dtype=np.uint32) & 0x7FFFFFFF).astype(np.int64)
         cats = dict(t.get("cats") or {})
@@ -627,7 +649,16 @@ def add_categorical_splits(trees: List[dict], cat_features, n_categories: int, s
             members = np.nonzero(rng.random(n_categories) < 0.4)[0]
             if members.size == 0:
                 members = np.array([int(rng.integers(0, n_categories))])
+            if edge_frac > 0 and erng.random() < edge_frac:
+                members = edge[n_edge % len(edge)]
+                n_edge += 1
             cats[int(i)] = members.astype(np.int32)
+        if ti < root_trees and cleft[0] != -1:
+            sindex = np.array(t["sindex"], dtype=np.uint32)
+            sindex[0] = (sindex[0] & np.uint32(0x80000000)) | \
+                np.uint32(cat_features[ti % cat_features.shape[0]])
+            t["sindex"] = sindex
+            cats[0] = edge[ti % len(edge)]
         if cats:
             t["cats"] = cats
     return trees

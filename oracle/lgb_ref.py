@@ -163,7 +163,10 @@ def rows_from_inputs(model: LGBRefModel, inputs) -> np.ndarray:
     return np.concatenate(blocks, axis=0)
 
 
-def leaf_index(model: LGBRefModel, X: np.ndarray) -> np.ndarray:
+def leaf_index(model: LGBRefModel, X: np.ndarray, trace=None) -> np.ndarray:
+    """Leaf index per (row, tree).  ``trace``, a list, receives one ``(tree,
+    rows, nodes, values, went_left)`` tuple of arrays for every visit of rows
+    to categorical nodes (the sibling of xgb_ref.leaf_index's)."""
     X = np.asarray(X, dtype=np.float64)
     X = np.where((np.abs(X) > K_ZERO_THRESHOLD) | np.isnan(X), X, 0.0)   # predictor row fill
     rows = X.shape[0]
@@ -188,7 +191,10 @@ def leaf_index(model: LGBRefModel, X: np.ndarray) -> np.ndarray:
             go_left = np.where(to_default, default_left, fval <= tr.threshold[n])
             cat = (dt & 1) != 0
             if cat.any():
-                go_left = np.where(cat, categorical_left(tr, n, raw), go_left)
+                # at the categorical nodes only: a numerical node's threshold is no bitset index
+                go_left[cat] = categorical_left(tr, n[cat], raw[cat])
+                if trace is not None:
+                    trace.append((t, idx[cat], n[cat], raw[cat], go_left[cat]))
             node[idx] = np.where(go_left, tr.left_child[n], tr.right_child[n])
         out[:, t] = ~node
     return out

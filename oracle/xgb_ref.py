@@ -15,10 +15,20 @@ the model load at :38-39.  Upstream algorithm (xgboost 0.82, not vendored in
   ``fvalue < split_cond`` -> left.
 * cpu_predictor.cc  PredValue/PredLoopSpecalize: psum = 0.0f; psum +=
   leaf for trees of the group in order; preds[row, g] (= base_margin) += psum.
+  xgboost >= 1.4 (PredictBatchByBlockOfRowsKernel) instead starts out_preds
+  at the base margin and adds each tree's leaf to it in order: the same
+  float32 additions with the base first (``minor_version`` tells which).
 * DMatrix from a numpy array (missing = NaN): NaN entries are missing.
   From a python list (model.py:46) 0.82 builds ``scipy.sparse.csr_matrix``:
   zeros are dropped (missing) and NaN stays a present value (never < split,
   so it goes right).
+* categorical splits (xgboost >= 1.7, tree_model.h GetNextNode /
+  common/categorical.h Decision; the rule include/treeinfer.h states for
+  TI_NODE_CAT_XGB): missing -> default child; ``x < 0`` or ``x >= 2^24``
+  (an invalid category; -0.0 is category 0) -> left; otherwise right iff
+  ``trunc(x)`` is in the node's category set.  The sets are kept as sorted
+  integer arrays (``XGBRefTree.cats``: node id -> codes), never as bitsets,
+  so this file shares nothing with the loader's ``cat_bits`` packing.
 * objectives: binary:logistic / reg:logistic 1/(1+exp(-x)) in float;
   multi:softprob softmax (float max, double sum); multi:softmax first argmax.
 """
@@ -26,7 +36,7 @@ from __future__ import annotations
 
 import struct
 from dataclasses import dataclass
-from typing import List
+from typing import Dict, List, Optional
 
 import numpy as np
 
@@ -37,6 +47,7 @@ class XGBRefTree:
     cright: np.ndarray
     sindex: np.ndarray
     value: np.ndarray   # float32 split condition or leaf value
+    cats: Optional[Dict[int, np.ndarray]] = None   # categorical nodes: node id -> sorted codes
 
 
 @dataclass
@@ -49,6 +60,7 @@ class XGBRefModel:
     major_version: int
     trees: List[XGBRefTree]
     tree_info: np.ndarray
+    minor_version: int = 0
 
 
 def read_xgb_binary(path: str) -> XGBRefModel:
@@ -109,8 +121,27 @@ def n_groups(m: XGBRefModel) -> int:
     return max(1, m.num_output_group, m.num_class)
 
 
-def leaf_index(m: XGBRefModel, X: np.ndarray, missing: str = "nan") -> np.ndarray:
-    """Leaf node id per (row, tree): RegTree::GetLeafIndex for every tree."""
+K_MAX_CAT = 16777216.0   # common::OutOfRangeCat: 2^24, the largest float32 run of integers
+
+
+def categorical_left(tr: XGBRefTree, node: np.ndarray, v: np.ndarray) -> np.ndarray:
+    """common::Decision for present values ``v`` at categorical nodes ``node``
+    (one entry per row): invalid categories go left, members of the set right."""
+    left = np.ones(node.shape[0], dtype=bool)
+    valid = ~((v < 0) | (v >= K_MAX_CAT) | np.isnan(v))
+    code = np.where(valid, v, 0).astype(np.int64)          # truncation toward zero
+    for n in np.unique(node):
+        at = (node == n) & valid
+        left[at] = ~np.isin(code[at], tr.cats[int(n)])
+    return left
+
+
+def leaf_index(m: XGBRefModel, X: np.ndarray, missing: str = "nan", trace=None) -> np.ndarray:
+    """Leaf node id per (row, tree): RegTree::GetLeafIndex for every tree.
+
+    ``trace``, a list, receives one ``(tree, rows, nodes, values, went_left)``
+    tuple of arrays for every visit of rows to categorical nodes (tests use it
+    to show which values a categorical node decided)."""
     X = np.asarray(X, dtype=np.float32)
     rows = X.shape[0]
     out = np.zeros((rows, len(m.trees)), dtype=np.int64)
@@ -131,6 +162,14 @@ def leaf_index(m: XGBRefModel, X: np.ndarray, missing: str = "nan") -> np.ndarra
                 is_missing = np.isnan(v)
             default_left = (tr.sindex[n] >> 31) != 0
             go_left = np.where(is_missing, default_left, v < tr.value[n])
+            if tr.cats:
+                cat = np.isin(n, np.fromiter(tr.cats, dtype=np.int64))
+                if cat.any():
+                    c = np.nonzero(cat)[0]
+                    go_left[c] = np.where(is_missing[c], default_left[c],
+                                          categorical_left(tr, n[c], v[c]))
+                    if trace is not None:
+                        trace.append((t, idx[c], n[c], v[c], go_left[c]))
             nid[idx] = np.where(go_left, tr.cleft[n], tr.cright[n])
         out[:, t] = nid
     return out
@@ -144,12 +183,15 @@ def predict(m: XGBRefModel, X: np.ndarray, output_margin: bool = False, pred_lea
     rows = leaves.shape[0]
     K = n_groups(m)
     margin = np.empty((rows, K), dtype=np.float32)
+    base_first = (m.major_version, m.minor_version) >= (1, 4)
     for g in range(K):
         psum = np.zeros(rows, dtype=np.float32)
+        if base_first:
+            psum = psum + base_margin(m)
         for t, tr in enumerate(m.trees):
             if m.tree_info[t] == g:
                 psum = psum + tr.value[leaves[:, t]]          # float32 + float32
-        margin[:, g] = base_margin(m) + psum                   # preds(base) += psum
+        margin[:, g] = psum if base_first else base_margin(m) + psum   # preds(base) += psum
     if output_margin:
         return margin if K > 1 else margin[:, 0]
     return transform(m.objective, margin)
@@ -175,10 +217,14 @@ def transform(objective: str, margin: np.ndarray) -> np.ndarray:
 
 
 def from_raw_trees(trees, tree_info, num_feature, num_class, base_score, objective,
-                   major_version: int = 0) -> XGBRefModel:
-    """Build a reference model from RegTree arrays (synthetic models)."""
+                   major_version: int = 0, minor_version: int = 0) -> XGBRefModel:
+    """Build a reference model from RegTree arrays (synthetic models); a
+    tree's ``cats`` (node id -> category codes, as the writers take them) makes
+    those nodes categorical."""
     rt = [XGBRefTree(np.asarray(t["cleft"], np.int64), np.asarray(t["cright"], np.int64),
-                     np.asarray(t["sindex"], np.uint64), np.asarray(t["value"], np.float32))
+                     np.asarray(t["sindex"], np.uint64), np.asarray(t["value"], np.float32),
+                     {int(n): np.unique(np.asarray(c, dtype=np.int64))
+                      for n, c in t["cats"].items()} if t.get("cats") else None)
           for t in trees]
     return XGBRefModel(base_score, num_feature, num_class, max(1, num_class), objective,
-                       major_version, rt, np.asarray(tree_info, np.int64))
+                       major_version, rt, np.asarray(tree_info, np.int64), minor_version)

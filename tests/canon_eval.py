@@ -4,14 +4,16 @@ encoding (thresholds, NaN / zero flags, leaf payloads, base, transform)
 reproduces the oracle, independently of the GPU kernels."""
 import numpy as np
 
-from kfserving_amd.forest import (NODE_CATEGORICAL, NODE_NAN_LEFT, NODE_ZERO_FLIP, OUT_LEAF, OUT_MARGIN,
-                                  T_ARGMAX, T_EXP, T_HINGE, T_IDENTITY, T_SIGMOID, T_SOFTMAX, T_STEP,
-                                  TI_F32, round_down_f32)
+from kfserving_amd.forest import (NODE_CAT_XGB, NODE_CATEGORICAL, NODE_NAN_LEFT, NODE_ZERO_FLIP,
+                                  OUT_LEAF, OUT_MARGIN, T_ARGMAX, T_EXP, T_HINGE, T_IDENTITY,
+                                  T_SIGMOID, T_SOFTMAX, T_STEP, TI_F32, round_down_f32)
 
 
 def cat_left(f, g, x):
-    """Categorical rule of the ABI: left iff bit trunc(x) of the node's bitset
-    is set; NaN, negatives and values outside int32 go right."""
+    """Categorical rules of the ABI.  LightGBM's: left iff bit trunc(x) of the
+    node's bitset is set; NaN, negatives and values outside int32 go right.
+    XGBoost's (NODE_CAT_XGB): NaN takes the default child (NODE_NAN_LEFT);
+    x < 0 or x >= 2^24 goes left; otherwise right iff that bit is set."""
     x = np.asarray(x, dtype=np.float64)
     bad = np.isnan(x) | (x >= 2147483648.0) | (x <= -2147483649.0)
     iv = np.where(bad, -1, np.trunc(np.where(bad, 0, x))).astype(np.int64)
@@ -19,7 +21,13 @@ def cat_left(f, g, x):
     nw = f.cat_nwords[g] if f.cat_nwords is not None else np.zeros_like(g)
     ok = (iv >= 0) & (iv // 32 < nw)
     w = f.cat_bits[np.where(ok, off + iv // 32, 0)].astype(np.int64) if ok.any() else 0
-    return ok & (((w >> np.where(ok, iv % 32, 0)) & 1) == 1)
+    member = ok & (((w >> np.where(ok, iv % 32, 0)) & 1) == 1)
+    xgb = (f.flags[g] & NODE_CAT_XGB) != 0
+    if not xgb.any():
+        return member
+    invalid = (x < 0) | (x >= 16777216.0)
+    left_xgb = np.where(np.isnan(x), (f.flags[g] & NODE_NAN_LEFT) != 0, invalid | ~member)
+    return np.where(xgb, left_xgb, member)
 
 
 def leaves(f, X):

@@ -13,11 +13,13 @@ import os
 import numpy as np
 import pytest
 
-from kfserving_amd.forest import (NODE_CAT_XGB, NODE_CATEGORICAL, NODE_NAN_LEFT, Forest, TI_F32)
+from kfserving_amd.forest import (NODE_CAT_XGB, NODE_CATEGORICAL, NODE_NAN_LEFT, OUT_LEAF, Forest,
+                                  TI_F32)
 from kfserving_amd.formats import load_xgboost_model
 from kfserving_amd.formats import ubjson
 from kfserving_amd.formats import xgboost_format as xf
 from kfserving_amd.formats.xgboost_format import XGBoostFormatError, parse_xgboost_bytes
+from tests import canon_eval
 
 KA_FILE = "xgb_categorical_ka.json"
 INF, NAN = float("inf"), float("nan")
@@ -107,36 +109,11 @@ def walk_doc(doc: dict, X) -> tuple:
 
 def forest_walk(f: Forest, X) -> np.ndarray:
     """Leaf ids of the canonical forest (the loader's arrays) on the host: the
-    rule as include/treeinfer.h states it, for checking the loader's output."""
-    X = np.asarray(X, dtype=np.float32)
-    out = np.zeros((X.shape[0], f.n_trees), dtype=np.int32)
-    for r in range(X.shape[0]):
-        for t in range(f.n_trees):
-            b = int(f.tree_offset[t])
-            n = 0
-            while f.feature[b + n] >= 0:
-                g = b + n
-                x = float(X[r, f.feature[g]])
-                fl = int(f.flags[g])
-                if fl & NODE_CATEGORICAL:
-                    assert fl & NODE_CAT_XGB
-                    if x != x:
-                        left = bool(fl & NODE_NAN_LEFT)
-                    elif x < 0 or x >= 16777216.0:
-                        left = True
-                    else:
-                        v = int(x)
-                        w = v // 32
-                        inset = w < f.cat_nwords[g] and \
-                            (int(f.cat_bits[f.cat_offset[g] + w]) >> (v % 32)) & 1
-                        left = not inset
-                elif x != x:
-                    left = bool(fl & NODE_NAN_LEFT)
-                else:
-                    left = x <= f.threshold[g]
-                n = int(f.left[g] if left else f.right[g])
-            out[r, t] = f.leaf_id[b + n]
-    return out
+    rule as include/treeinfer.h states it (tests/canon_eval.py), for checking
+    the loader's output.  Every categorical node must carry XGBoost's rule."""
+    cat = (f.feature >= 0) & ((f.flags & NODE_CATEGORICAL) != 0)
+    assert np.all((f.flags[cat] & NODE_CAT_XGB) != 0)
+    return canon_eval.predict(f, np.asarray(X, dtype=np.float32), OUT_LEAF)
 
 
 def synthetic_cat_model(n_trees=12, depth=4, n_features=6, seed=3, num_class=0,
