@@ -35,7 +35,6 @@
 #include "treeinfer.h"
 #include "treeinfer_kernels.h"
 #include "treeinfer_dispatch.h"
-#include "treeinfer_cheap.h"
 
 using ti::ExpNode;
 using ti::HeapNode;
@@ -2154,37 +2153,12 @@ int upload_device(ti_forest* f, DeviceForest& d, int device) {
 }
 
 // ----------------------------------------------------------------- launch
+// plan_launch decides what does not depend on the batch -- tile rows, block,
+// LDS bytes, the kernel's key and its arguments -- and launch() adds the batch
+// and holds the one launch site of the predict kernels.  The kernels live in
+// one translation unit per (input, accumulator) type pair (treeinfer_k_*.hip,
+// compiled in parallel); ti::select finds one from its key (treeinfer_dispatch.h).
 using ti::KernelFn;
-
-// Kernel instantiations live in one translation unit per (input, accumulator)
-// type pair (treeinfer_k_*.hip, compiled in parallel); see treeinfer_dispatch.h.
-KernelFn select_kernel(int layout, int xdt, int accum, int K, bool fl, bool z) {
-  if (xdt == TI_F32 && accum == TI_F32) return ti::kernels_ff(layout, K, fl, z, false, 0);
-  if (xdt == TI_F32 && accum == TI_F64) return ti::kernels_fd(layout, K, fl, z, false, 0);
-  if (xdt == TI_F64 && accum == TI_F64) return ti::kernels_dd(layout, K, fl, z, false, 0);
-  return ti::kernels_df(layout, K, fl, z, false, 0);
-}
-
-KernelFn select_bheap(int xdt, int accum, int K, bool b16, int pf) {
-  if (xdt == TI_F32 && accum == TI_F32) return ti::kernels_ff(3, K, true, false, b16, pf);
-  if (xdt == TI_F32 && accum == TI_F64) return ti::kernels_fd(3, K, true, false, b16, pf);
-  if (xdt == TI_F64 && accum == TI_F64) return ti::kernels_dd(3, K, true, false, b16, pf);
-  return ti::kernels_df(3, K, true, false, b16, pf);
-}
-
-KernelFn select_rexplicit(int xdt, int accum, int K, bool z, int ilp) {
-  if (xdt == TI_F32 && accum == TI_F32) return ti::kernels_ff(6, K, true, z, true, ilp);
-  if (xdt == TI_F32 && accum == TI_F64) return ti::kernels_fd(6, K, true, z, true, ilp);
-  if (xdt == TI_F64 && accum == TI_F64) return ti::kernels_dd(6, K, true, z, true, ilp);
-  return ti::kernels_df(6, K, true, z, true, ilp);
-}
-
-KernelFn select_lexplicit(int xdt, int accum, int K, bool z, int ilp) {
-  if (xdt == TI_F32 && accum == TI_F32) return ti::kernels_ff(7, K, true, z, true, ilp);
-  if (xdt == TI_F32 && accum == TI_F64) return ti::kernels_fd(7, K, true, z, true, ilp);
-  if (xdt == TI_F64 && accum == TI_F64) return ti::kernels_dd(7, K, true, z, true, ilp);
-  return ti::kernels_df(7, K, true, z, true, ilp);
-}
 
 // Columns per pass of the record layouts' coalesced binning through the stage
 // area (rx_stage_bins): a multiple of 8 that fits `bytes` for R rows, at most
@@ -2194,41 +2168,6 @@ int32_t bin_chunk_for(size_t bytes, int R, int xdt, int F) {
   size_t c = (bytes / per_col) & ~size_t(7);
   c = std::min(c, static_cast<size_t>((F + 7) & ~7));
   return c >= 8 ? static_cast<int32_t>(c) : 0;
-}
-
-KernelFn select_texplicit(int xdt, int accum, int K, bool z, int ilp, bool b8) {
-  if (xdt == TI_F32 && accum == TI_F32) return ti::kernels_ff(9, K, true, z, !b8, ilp);
-  if (xdt == TI_F32 && accum == TI_F64) return ti::kernels_fd(9, K, true, z, !b8, ilp);
-  if (xdt == TI_F64 && accum == TI_F64) return ti::kernels_dd(9, K, true, z, !b8, ilp);
-  return ti::kernels_df(9, K, true, z, !b8, ilp);
-}
-
-KernelFn select_t8explicit(int xdt, int accum, int K, bool z, int ilp) {   // layout 9, compact u8 bottom
-  if (xdt == TI_F32 && accum == TI_F32) return ti::kernels_ff(11, K, true, z, false, ilp);
-  if (xdt == TI_F32 && accum == TI_F64) return ti::kernels_fd(11, K, true, z, false, ilp);
-  if (xdt == TI_F64 && accum == TI_F64) return ti::kernels_dd(11, K, true, z, false, ilp);
-  return ti::kernels_df(11, K, true, z, false, ilp);
-}
-
-KernelFn select_t16explicit(int xdt, int accum, int K, bool z, int ilp) {   // layout 9, compact u16 bottom
-  if (xdt == TI_F32 && accum == TI_F32) return ti::kernels_ff(12, K, true, z, true, ilp);
-  if (xdt == TI_F32 && accum == TI_F64) return ti::kernels_fd(12, K, true, z, true, ilp);
-  if (xdt == TI_F64 && accum == TI_F64) return ti::kernels_dd(12, K, true, z, true, ilp);
-  return ti::kernels_df(12, K, true, z, true, ilp);
-}
-
-KernelFn select_t16split(int xdt, int accum, int K, bool z) {   // layout 9, u16, two lanes a row
-  if (xdt == TI_F32 && accum == TI_F32) return ti::kernels_ff(13, K, true, z, true, 4);
-  if (xdt == TI_F32 && accum == TI_F64) return ti::kernels_fd(13, K, true, z, true, 4);
-  if (xdt == TI_F64 && accum == TI_F64) return ti::kernels_dd(13, K, true, z, true, 4);
-  return ti::kernels_df(13, K, true, z, true, 4);
-}
-
-KernelFn select_hexplicit(int xdt, int accum, int K, bool z, int ilp) {
-  if (xdt == TI_F32 && accum == TI_F32) return ti::kernels_ff(8, K, true, z, true, ilp);
-  if (xdt == TI_F32 && accum == TI_F64) return ti::kernels_fd(8, K, true, z, true, ilp);
-  if (xdt == TI_F64 && accum == TI_F64) return ti::kernels_dd(8, K, true, z, true, ilp);
-  return ti::kernels_df(8, K, true, z, true, ilp);
 }
 
 std::mutex g_attr_mu;
@@ -2298,16 +2237,63 @@ bool bheap_fixed(const ti_forest* f, int xdt, int kind) {
          bi.stride == ti::kFixTree && static_cast<uint32_t>(bi.words) * 2048u <= ti::kFixFlag;
 }
 
-// Stage size S (trees) of the heap layouts (0, 10) for tiles of R rows: as
-// many trees as keep the workgroups-per-CU count that the smallest useful
-// stage (kTilp trees) allows -- occupancy is what hides the LDS latency of the
-// walk (measured: 3 WG/CU beat 2 WG/CU by 1.7x at F = 28) -- capped by the
-// prefetch registers (kPf x 16 B x R).  `fixed`: the LDS bytes before the
-// stage (feature image + NaN flag word).  TI_HEAP_LDS_KB overrides with a
-// fixed per-workgroup budget.  0: not even one record fits.
+// Rows per tile and the LDS bytes of the feature (or bin) image, for batches
+// of input type xdt.  The heap, binned and record images fixed R at create
+// time (their meta words hold [F][R] byte offsets); the float explicit layout
+// takes the largest R whose feature image fits.  !feat_lds: features stay in
+// HBM, tiles of 256 rows.
+struct Tile {
+  int R;
+  bool feat_lds;
+  size_t feat_bytes;
+};
+
+Tile tile_for(const ti_forest* f, int xdt) {
+  const size_t xs = dtype_size(xdt);
+  const int ii = xdt == TI_F64 ? 1 : 0;
+  const bool rec = f->layout >= 6 && f->layout <= 9;
+  int R;
+  if (f->layout == 0 || f->layout == 10) {
+    R = xdt == TI_F64 ? f->rows64 : f->rows32;
+  } else if (f->layout == 3) {
+    R = f->bh[ii].rows;
+  } else if (rec) {
+    R = f->rx[ii].rows;
+  } else {
+    R = 256;
+    while (R > 64 && static_cast<size_t>(f->F) * R * xs > kFeatLdsMax) R >>= 1;
+    if (static_cast<size_t>(f->F) * R * xs > kFeatLdsMax) R = 0;
+  }
+  Tile t;
+  t.feat_lds = R > 0;
+  t.R = t.feat_lds ? R : 256;
+  t.feat_bytes = t.feat_lds ? align16(static_cast<size_t>(f->F) * t.R * xs) : 0;
+  if (f->layout == 3) t.feat_bytes = static_cast<size_t>(f->bh[ii].words) * t.R * 4;
+  if (rec) t.feat_bytes = static_cast<size_t>(f->rx[ii].words) * t.R * 4;
+  return t;
+}
+
+// The stage-size rule of the heap layouts and the binned heap: from S trees,
+// grow by `step` (the trees a lane walks at once) while the workgroups-per-CU
+// count of the first size holds -- occupancy is what hides the LDS latency of
+// the walk (measured: 3 WG/CU beat 2 WG/CU by 1.7x at F = 28) -- within `cap`
+// (the prefetch registers) and the forest.  `fixed`: the LDS bytes before the
+// stage; area(n): those of a stage of n trees.
+template <typename Area>
+int64_t grow_stage(int64_t S, int64_t step, int64_t cap, int64_t T, size_t fixed, Area area) {
+  auto wgs = [&](int64_t n) { return kLdsPerCu / (fixed + area(n)); };
+  const size_t best = S >= 1 ? wgs(S) : 0;
+  while (S + step <= cap && S + step <= T && wgs(S + step) >= best) S += step;
+  return S;
+}
+
+// Stage size S (trees) of the heap layouts (0, 10) for tiles of R rows: the
+// smallest useful stage (kTilp trees, fewer if LDS is short) grown by
+// grow_stage, capped by the prefetch registers (kPf x 16 B x R).  `fixed`:
+// feature image + NaN flag word.  TI_HEAP_LDS_KB overrides with a fixed
+// per-workgroup budget.  0: not even one record fits.
 int64_t heap_stage_trees(const ti_forest* f, int64_t stride_b, size_t fixed, int R) {
   const int64_t cap = static_cast<int64_t>(ti::kPf) * 16 * R / stride_b;
-  auto wgs = [&](int64_t n) { return kLdsPerCu / (fixed + static_cast<size_t>(n * stride_b)); };
   static const int budget_kb = env_int("TI_HEAP_LDS_KB", 0);
   int64_t S;
   if (budget_kb > 0) {
@@ -2317,9 +2303,8 @@ int64_t heap_stage_trees(const ti_forest* f, int64_t stride_b, size_t fixed, int
   } else {
     S = std::min<int64_t>(ti::kTilp, cap);
     while (S > 1 && fixed + static_cast<size_t>(S * stride_b) > kLdsPerCu) --S;
-    const size_t best = S >= 1 ? wgs(S) : 0;
-    while (S + ti::kTilp <= cap && S + ti::kTilp <= f->T && wgs(S + ti::kTilp) >= best)
-      S += ti::kTilp;
+    S = grow_stage(S, ti::kTilp, cap, f->T, fixed,
+                   [&](int64_t n) { return static_cast<size_t>(n * stride_b); });
   }
   if (S < 1 || fixed + static_cast<size_t>(S * stride_b) > kLdsPerCu) return 0;
   S = std::min<int64_t>(S, cap);
@@ -2327,37 +2312,45 @@ int64_t heap_stage_trees(const ti_forest* f, int64_t stride_b, size_t fixed, int
   return S;
 }
 
-int launch(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows, int32_t cols,
-           int64_t stride, int kind, void* out, hipStream_t stream) {
-  if (rows <= 0) return TI_OK;
-  const size_t xs = dtype_size(xdt);
-  // rows per tile = threads per workgroup; the heap images fixed it at create
-  // time (their meta words hold [F][R] byte offsets)
-  int R;
-  if (f->layout == 0 || f->layout == 10) {
-    R = xdt == TI_F64 ? f->rows64 : f->rows32;
-  } else if (f->layout == 3) {
-    R = f->bh[xdt == TI_F64 ? 1 : 0].rows;
-  } else if (f->layout >= 6 && f->layout <= 9) {
-    R = f->rx[xdt == TI_F64 ? 1 : 0].rows;
-  } else {
-    R = 256;
-    while (R > 64 && static_cast<size_t>(f->F) * R * xs > kFeatLdsMax) R >>= 1;
-    if (static_cast<size_t>(f->F) * R * xs > kFeatLdsMax) R = 0;
-  }
-  const bool feat_lds = R > 0;
-  if (!feat_lds) R = 256;
-  size_t feat_bytes = feat_lds ? align16(static_cast<size_t>(f->F) * R * xs) : 0;
-  if (f->layout == 3) feat_bytes = static_cast<size_t>(f->bh[xdt == TI_F64 ? 1 : 0].words) * R * 4;
-  if (f->layout >= 6 && f->layout <= 9)
-    feat_bytes = static_cast<size_t>(f->rx[xdt == TI_F64 ? 1 : 0].words) * R * 4;
+// The same for a created heap forest and batches of input type xdt: what
+// plan_launch stages and ti_forest_get_info reports.
+int64_t heap_stage_trees(const ti_forest* f, int xdt) {
+  const Tile t = tile_for(f, xdt);
+  return heap_stage_trees(f, xdt == TI_F64 ? f->stride64 : f->stride32, t.feat_bytes + 16, t.R);
+}
 
-  KArgs a;
+// Everything about a launch that does not depend on the batch.
+struct LaunchPlan {
+  ti::KernelKey key;
+  int R;        // rows per tile
+  int block;    // threads per workgroup: R, or 2R for the two-lane walk
+  size_t lds;   // dynamic LDS bytes
+  KArgs a;      // all but X, n_rows, row_stride, n_cols and out
+};
+
+// Plans the launch of forest f (device copy d) for batches of input type xdt
+// and output `kind`.  Host arithmetic only: it makes no HIP call, and reads
+// the knobs TI_BHEAP_FIX / TI_BHEAP_NG (every call) and TI_HEAP_LDS_KB /
+// TI_BHEAP_STAGE (once).
+int plan_launch(const ti_forest* f, const DeviceForest& d, int xdt, int kind, LaunchPlan* p) {
+  const size_t xs = dtype_size(xdt);
+  const int ii = xdt == TI_F64 ? 1 : 0;
+  const Tile t = tile_for(f, xdt);
+  const int R = t.R;
+  p->R = R;
+  p->block = R;
+  p->lds = t.feat_bytes + 16;   // feature image + NaN flag word
+
+  ti::KernelKey& key = p->key;
+  key = ti::KernelKey{};
+  key.x64 = xdt == TI_F64;
+  key.acc64 = f->accum == TI_F64;
+  key.K = f->K;
+  key.feat_lds = t.feat_lds;
+  key.zero_rule = f->zero_rule != 0;
+
+  KArgs& a = p->a;
   std::memset(&a, 0, sizeof(a));
-  a.X = X;
-  a.n_rows = rows;
-  a.row_stride = stride;
-  a.n_cols = cols;
   a.n_features = f->F;
   a.n_trees = f->T;
   a.n_groups = f->K;
@@ -2371,153 +2364,77 @@ int launch(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows, 
   a.average_divisor = f->divisor;
   for (int k = 0; k < ti::kMaxGroups; ++k) a.base[k] = f->base[k];
   a.tree_group = d.tree_group;
-  a.out = out;
 
-  size_t lds = feat_bytes + 16;
   if (f->layout == 0 || f->layout == 10) {
+    // [feature image][flag][stage area = S tree records]
     const int64_t stride_b = xdt == TI_F64 ? f->stride64 : f->stride32;
     a.trees = xdt == TI_F64 ? d.heap64 : d.heap32;
     a.tree_stride = stride_b;
     a.heap_leaf_ids = d.heap_leaf_ids;
     a.depth = f->depth;
-    const size_t fixed = feat_bytes + 16;   // feature image + NaN flag word
-    const int64_t S = heap_stage_trees(f, stride_b, fixed, R);
+    const int64_t S = heap_stage_trees(f, xdt);
     if (S < 1) return fail(TI_ERR_UNSUPPORTED, "heap tree record does not fit in LDS");
     a.stage_trees = static_cast<int32_t>(S);
-    lds = fixed + static_cast<size_t>(S * stride_b);
-    if (f->layout == 10) {   // categorical heap: its own kernels, always an LDS feature image
-      if (!feat_lds) return fail(TI_ERR_UNSUPPORTED, "categorical heap needs the LDS feature image");
-      KernelFn fn = ti::kernels_cat(xdt == TI_F64, f->accum == TI_F64, f->K, f->zero_rule != 0,
-                                    f->has_cat_xgb != 0);
-      int rc = ensure_lds_attr(d.device, fn);
-      if (rc) return rc;
-      const int64_t grid = (rows + R - 1) / R;
-      if (grid > 0x7fffffff) return fail(TI_ERR_INVALID, "too many rows for one launch");
-      occ_note(fn, R, lds);
-      hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(grid)), dim3(R), lds, stream, a);
-      TI_HIP(hipGetLastError());
-      return TI_OK;
+    p->lds += static_cast<size_t>(S * stride_b);
+    key.walk = ti::Walk::Heap;
+    if (f->layout == 10) {   // categorical heap: always an LDS feature image
+      if (!t.feat_lds) return fail(TI_ERR_UNSUPPORTED, "categorical heap needs the LDS feature image");
+      key.walk = f->has_cat_xgb != 0 ? ti::Walk::CatHeapXgb : ti::Walk::CatHeapLgb;
     }
   } else if (f->layout == 3) {
     // binned heap: [bin image][flag][stage area = S tree records, also the
-    // binning temp of >= 8 columns].  S as for the heap layout: the most
-    // trees that keep the best workgroups-per-CU count, capped by the
-    // prefetch registers (PF x 16 B x R).
-    const int ii = xdt == TI_F64 ? 1 : 0;
+    // binning temp of >= 8 columns].  S by grow_stage from kBTilp trees,
+    // capped by the prefetch registers (PF x 16 B x R); unlike the heap
+    // layouts no LDS-fit check, and TI_BHEAP_STAGE forces a size.
     const ti_forest::BinImage& bi = f->bh[ii];
     const int64_t stride_b = bi.stride;
-    const size_t fixed = align16(feat_bytes + 4);
+    const size_t fixed = align16(t.feat_bytes + 4);
     const size_t temp_min = 8 * static_cast<size_t>(R) * xs;
     auto area = [&](int64_t n) { return std::max(static_cast<size_t>(n * stride_b), temp_min); };
-    auto wgs = [&](int64_t n) { return kLdsPerCu / (fixed + area(n)); };
     const int64_t cap = static_cast<int64_t>(8) * 16 * R / stride_b;
     int64_t S = std::min<int64_t>(ti::kBTilp, cap);
     if (S < 1) return fail(TI_ERR_UNSUPPORTED, "binned heap tree record does not fit the stage");
-    const size_t best = wgs(S);
-    while (S + ti::kBTilp <= cap && S + ti::kBTilp <= f->T && wgs(S + ti::kBTilp) >= best) S += ti::kBTilp;
+    S = grow_stage(S, ti::kBTilp, cap, f->T, fixed, area);
     static const int force_s = env_int("TI_BHEAP_STAGE", 0);
     if (force_s > 0) S = std::min<int64_t>(force_s, cap);
     S = std::min<int64_t>(S, f->T);
-    const int pf = S * stride_b <= static_cast<int64_t>(4) * 16 * R ? 4 : 8;
-    a.X = X;
     a.bin_mask = bi.mask;
     a.bin_kary = bi.kary;
     a.trees = d.bh_img[ii];
     a.tree_stride = stride_b;
     a.heap_leaf_ids = d.heap_leaf_ids;
-    const bool fix_perm = d.bh_fix_img != nullptr && bheap_fixed(f, xdt, kind);
     a.depth = f->depth;
-    a.stage_trees = static_cast<int32_t>(S);
     a.bin_tbl = d.bh_tbl[ii];
     a.bin_L = bi.L;
     a.bin_words = bi.words;
-    a.stage_off = static_cast<int32_t>(fixed);
-    const size_t ar = area(S);
-    a.bin_chunk = static_cast<int32_t>(std::min<size_t>((ar / (static_cast<size_t>(R) * xs)) & ~size_t(7),
-                                                        static_cast<size_t>(f->F + 7) & ~size_t(7)));
-    lds = fixed + ar;
-    KernelFn fn = select_bheap(xdt, f->accum, f->K, bi.b16 != 0, pf);
-    if (bheap_fixed(f, xdt, kind)) {
+    key.bins16 = bi.b16 != 0;
+    if (!bheap_fixed(f, xdt, kind)) {
+      key.walk = ti::Walk::BinHeap;
+      key.prefetch = S * stride_b <= static_cast<int64_t>(4) * 16 * R ? 4 : 8;
+      const size_t ar = area(S);
+      a.stage_trees = static_cast<int32_t>(S);
+      a.stage_off = static_cast<int32_t>(fixed);
+      a.bin_chunk = static_cast<int32_t>(std::min<size_t>((ar / (static_cast<size_t>(R) * xs)) & ~size_t(7),
+                                                          static_cast<size_t>(f->F + 7) & ~size_t(7)));
+      p->lds = fixed + ar;
+    } else {
       // fixed layout (bheap_fix_kernel): [bins][flag][NG groups of 4 trees at
       // kFixStage]; the binning goes through the stage area, 4 NG columns at a
       // time.  NG = 1: 38,912 B, 4 workgroups (32 waves) per CU
       const int ng = std::min(2, std::max(1, env_int("TI_BHEAP_NG", 1)));
-      fn = ti::kernels_ff(10, f->K, true, false, bi.b16 != 0, ng);
+      key.walk = ti::Walk::BinHeapFixed;
+      key.groups = ng;
       a.stage_trees = 4 * ng;
       a.bin_chunk = 4 * ng;
       a.stage_off = static_cast<int32_t>(ti::kFixStage);
-      if (fix_perm) a.trees = d.bh_fix_img;   // same walk, hot pair slots first
-      lds = ti::kFixStage + static_cast<size_t>(4 * ng) * ti::kFixTree;
+      if (d.bh_fix_img != nullptr) a.trees = d.bh_fix_img;   // same walk, hot pair slots first
+      p->lds = ti::kFixStage + static_cast<size_t>(4 * ng) * ti::kFixTree;
     }
-    int rc = ensure_lds_attr(d.device, fn);
-    if (rc) return rc;
-    const int64_t grid = (rows + R - 1) / R;
-    if (grid > 0x7fffffff) return fail(TI_ERR_INVALID, "too many rows for one launch");
-    occ_note(fn, R, lds);
-  hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(grid)), dim3(R), lds, stream, a);
-    TI_HIP(hipGetLastError());
-    return TI_OK;
-  } else if (f->layout == 6) {
-    const int ii = xdt == TI_F64 ? 1 : 0;
+  } else if (f->layout >= 6 && f->layout <= 9) {
+    // record layouts: [bin image][flag][stage area (7, 8, 9)]
     const ti_forest::RecExplicit& rx = f->rx[ii];
-    a.rx_recs = d.rx_recs[ii];
-    a.rx_base = d.rx_base;
-    a.rx_nint = d.rx_nint;
-    a.leaf_base = d.leaf_base;
-    a.rx_slots = static_cast<uint32_t>(f->rx_slots);
-    a.leaves = d.leaves;
-    a.exp_leaf_ids = d.exp_leaf_ids;
-    a.bin_tbl = d.bx_tbl[ii];
-    a.bin_L = rx.L;
-    a.bin_kary = rx.kary;
-    a.bin_words = rx.words;
-    lds = feat_bytes + 16;
-    KernelFn fn = select_rexplicit(xdt, f->accum, f->K, f->zero_rule != 0, f->rx_ilp);
-    int rc = ensure_lds_attr(d.device, fn);
-    if (rc) return rc;
-    const int64_t grid = (rows + R - 1) / R;
-    if (grid > 0x7fffffff) return fail(TI_ERR_INVALID, "too many rows for one launch");
-    occ_note(fn, R, lds);
-  hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(grid)), dim3(R), lds, stream, a);
-    TI_HIP(hipGetLastError());
-    return TI_OK;
-  } else if (f->layout == 7) {
-    const int ii = xdt == TI_F64 ? 1 : 0;
-    const ti_forest::RecExplicit& rx = f->rx[ii];
-    a.rx_recs = d.rx_recs[ii];
-    a.rx_base = d.rx_base;
-    a.rx_nint = d.rx_nint;
-    a.leaf_base = d.leaf_base;
-    a.rx_slots = static_cast<uint32_t>(f->rx_slots);
-    a.leaves = d.leaves;
-    a.exp_leaf_ids = d.exp_leaf_ids;
-    a.bin_tbl = d.bx_tbl[ii];
-    a.bin_L = rx.L;
-    a.bin_kary = rx.kary;
-    a.bin_words = rx.words;
-    a.stage_start = d.lx_stage;
-    a.n_stages = static_cast<int32_t>(f->h_lx_stage.size() - 1);
-    a.stage_off = static_cast<int32_t>(align16(feat_bytes + 4));
-    lds = std::max(static_cast<size_t>(a.stage_off) + static_cast<size_t>(f->lx_stage_cap), kLxMinLds);
-    if (lds > kLdsPerCu || static_cast<int64_t>(kLxPf) * 16 * R < f->lx_stage_cap)
-      return fail(TI_ERR_UNSUPPORTED, "staged record layout exceeds LDS");
-    a.bin_chunk = bin_chunk_for(static_cast<size_t>(f->lx_stage_cap), R, xdt, f->F);
-    KernelFn fn = select_lexplicit(xdt, f->accum, f->K, f->zero_rule != 0, f->lx_ilp);
-    int rc = ensure_lds_attr(d.device, fn);
-    if (rc) return rc;
-    const int64_t grid = (rows + R - 1) / R;
-    if (grid > 0x7fffffff) return fail(TI_ERR_INVALID, "too many rows for one launch");
-    occ_note(fn, R, lds);
-  hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(grid)), dim3(R), lds, stream, a);
-    TI_HIP(hipGetLastError());
-    return TI_OK;
-  } else if (f->layout == 9) {
-    const int ii = xdt == TI_F64 ? 1 : 0;
-    const ti_forest::RecExplicit& rx = f->rx[ii];
-    a.trees = reinterpret_cast<const unsigned char*>(d.hx_top[ii]);
-    a.depth = f->hx_top;
-    a.rx_base = d.rx_base;   // tree byte offsets in the image
-    a.rx_nint = d.rx_nint;   // bottom internal nodes
+    a.rx_base = d.rx_base;   // 9: tree byte offsets in the image
+    a.rx_nint = d.rx_nint;   // 9: bottom internal nodes
     a.leaf_base = d.leaf_base;
     a.leaves = d.leaves;
     a.exp_leaf_ids = d.exp_leaf_ids;
@@ -2525,63 +2442,45 @@ int launch(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows, 
     a.bin_L = rx.L;
     a.bin_kary = rx.kary;
     a.bin_words = rx.words;
-    a.stage_start = d.lx_stage;
-    a.n_stages = static_cast<int32_t>(f->h_lx_stage.size() - 1);
-    a.stage_off = static_cast<int32_t>(align16(feat_bytes + 4));
-    lds = std::max(static_cast<size_t>(a.stage_off) + static_cast<size_t>(f->lx_stage_cap), kLxMinLds);
-    if (lds > kLdsPerCu || static_cast<int64_t>(kLxPf) * 16 * R < f->lx_stage_cap)
-      return fail(TI_ERR_UNSUPPORTED, "heap-top staged layout exceeds LDS");
-    a.bin_chunk = bin_chunk_for(static_cast<size_t>(f->lx_stage_cap), R, xdt, f->F);
-    a.tx_pos = d.tx8_pos;
-    a.tx_vals = d.tx8_val;
-    a.tx_ord = d.tx8_ord;
-    a.bin_mask = f->tx16_mask;
-    KernelFn fn = f->tx8 == 3 ? select_t16split(xdt, f->accum, f->K, f->zero_rule != 0)
-                : f->tx8 == 2 ? select_t16explicit(xdt, f->accum, f->K, f->zero_rule != 0, f->lx_ilp)
-                : f->tx8 ? select_t8explicit(xdt, f->accum, f->K, f->zero_rule != 0, f->lx_ilp)
-                         : select_texplicit(xdt, f->accum, f->K, f->zero_rule != 0, f->lx_ilp, rx.b8 != 0);
-    int rc = ensure_lds_attr(d.device, fn);
-    if (rc) return rc;
-    const int64_t grid = (rows + R - 1) / R;
-    if (grid > 0x7fffffff) return fail(TI_ERR_INVALID, "too many rows for one launch");
-    const int block = f->tx8 == 3 ? 2 * R : R;   // two lanes a row: 2R threads
-    if (block > 512) return fail(TI_ERR_UNSUPPORTED, "two-lane walk needs tiles of <= 256 rows");
-    occ_note(fn, block, lds);
-  hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(grid)), dim3(block), lds, stream, a);
-    TI_HIP(hipGetLastError());
-    return TI_OK;
-  } else if (f->layout == 8) {
-    const int ii = xdt == TI_F64 ? 1 : 0;
-    const ti_forest::RecExplicit& rx = f->rx[ii];
-    a.rx_recs = d.rx_recs[ii];
-    a.rx_base = d.rx_base;
-    a.rx_nint = d.rx_nint;
-    a.leaf_base = d.leaf_base;
-    a.rx_slots = static_cast<uint32_t>(f->rx_slots);
-    a.leaves = d.leaves;
-    a.exp_leaf_ids = d.exp_leaf_ids;
-    a.bin_tbl = d.bx_tbl[ii];
-    a.bin_L = rx.L;
-    a.bin_kary = rx.kary;
-    a.bin_words = rx.words;
-    a.trees = reinterpret_cast<const unsigned char*>(d.hx_top[ii]);
-    a.depth = f->hx_top;
-    a.tree_stride = static_cast<int64_t>(8) << f->hx_top;   // 2^(D0+1) u32
-    a.stage_trees = f->hx_stage;
-    a.stage_off = static_cast<int32_t>(align16(feat_bytes + 4));
-    lds = static_cast<size_t>(a.stage_off) + static_cast<size_t>(f->hx_stage) * a.tree_stride;
-    if (lds > kLdsPerCu || static_cast<int64_t>(kHxPf) * 16 * R < f->hx_stage * a.tree_stride)
-      return fail(TI_ERR_UNSUPPORTED, "heap-top layout exceeds LDS");
-    a.bin_chunk = bin_chunk_for(static_cast<size_t>(f->hx_stage) * a.tree_stride, R, xdt, f->F);
-    KernelFn fn = select_hexplicit(xdt, f->accum, f->K, f->zero_rule != 0, f->hx_ilp);
-    int rc = ensure_lds_attr(d.device, fn);
-    if (rc) return rc;
-    const int64_t grid = (rows + R - 1) / R;
-    if (grid > 0x7fffffff) return fail(TI_ERR_INVALID, "too many rows for one launch");
-    occ_note(fn, R, lds);
-  hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(grid)), dim3(R), lds, stream, a);
-    TI_HIP(hipGetLastError());
-    return TI_OK;
+    if (f->layout != 9) {
+      a.rx_recs = d.rx_recs[ii];
+      a.rx_slots = static_cast<uint32_t>(f->rx_slots);
+    }
+    if (f->layout >= 8) {   // heap top
+      a.trees = reinterpret_cast<const unsigned char*>(d.hx_top[ii]);
+      a.depth = f->hx_top;
+    }
+    if (f->layout != 6) a.stage_off = static_cast<int32_t>(align16(t.feat_bytes + 4));
+    if (f->layout == 7 || f->layout == 9) {   // stages of whole trees, at most lx_stage_cap bytes
+      a.stage_start = d.lx_stage;
+      a.n_stages = static_cast<int32_t>(f->h_lx_stage.size() - 1);
+      p->lds = std::max(static_cast<size_t>(a.stage_off) + static_cast<size_t>(f->lx_stage_cap), kLxMinLds);
+      if (p->lds > kLdsPerCu || static_cast<int64_t>(kLxPf) * 16 * R < f->lx_stage_cap)
+        return fail(TI_ERR_UNSUPPORTED, f->layout == 7 ? "staged record layout exceeds LDS"
+                                                       : "heap-top staged layout exceeds LDS");
+      a.bin_chunk = bin_chunk_for(static_cast<size_t>(f->lx_stage_cap), R, xdt, f->F);
+    } else if (f->layout == 8) {   // stages of hx_stage heap tops
+      a.tree_stride = static_cast<int64_t>(8) << f->hx_top;   // 2^(D0+1) u32
+      a.stage_trees = f->hx_stage;
+      p->lds = static_cast<size_t>(a.stage_off) + static_cast<size_t>(f->hx_stage) * a.tree_stride;
+      if (p->lds > kLdsPerCu || static_cast<int64_t>(kHxPf) * 16 * R < f->hx_stage * a.tree_stride)
+        return fail(TI_ERR_UNSUPPORTED, "heap-top layout exceeds LDS");
+      a.bin_chunk = bin_chunk_for(static_cast<size_t>(f->hx_stage) * a.tree_stride, R, xdt, f->F);
+    }
+    if (f->layout == 9) {
+      a.tx_pos = d.tx8_pos;
+      a.tx_vals = d.tx8_val;
+      a.tx_ord = d.tx8_ord;
+      a.bin_mask = f->tx16_mask;
+      key.walk = f->tx8 == 3 ? ti::Walk::BottomU16Split : f->tx8 == 2 ? ti::Walk::BottomU16
+                 : f->tx8 ? ti::Walk::BottomU8 : ti::Walk::HeapTopStaged;
+      key.bins16 = rx.b8 == 0;
+      if (f->tx8 == 3) p->block = 2 * R;   // two lanes a row
+    } else {
+      key.walk = f->layout == 6 ? ti::Walk::Record
+                 : f->layout == 7 ? ti::Walk::StagedRecord : ti::Walk::HeapTopRecord;
+    }
+    key.ilp = f->layout == 6 ? f->rx_ilp : f->layout == 8 ? f->hx_ilp : f->lx_ilp;
   } else {
     a.nodes = d.nodes;
     a.thr64 = d.thr64;
@@ -2591,14 +2490,31 @@ int launch(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows, 
     a.leaves = d.leaves;
     a.exp_leaf_ids = d.exp_leaf_ids;
     a.cat_words = d.cat_words;
+    key.walk = ti::Walk::Explicit;
   }
-  KernelFn fn = select_kernel(f->layout, xdt, f->accum, f->K, feat_lds, f->zero_rule != 0);
-  int rc = ensure_lds_attr(d.device, fn);
+  return TI_OK;
+}
+
+// The one launch site of the predict kernels: the plan, the batch, the grid.
+int launch(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows, int32_t cols,
+           int64_t stride, int kind, void* out, hipStream_t stream) {
+  if (rows <= 0) return TI_OK;
+  LaunchPlan p;
+  int rc = plan_launch(f, d, xdt, kind, &p);
   if (rc) return rc;
-  const int64_t grid = (rows + R - 1) / R;
+  p.a.X = X;
+  p.a.n_rows = rows;
+  p.a.row_stride = stride;
+  p.a.n_cols = cols;
+  p.a.out = out;
+  KernelFn fn = ti::select(p.key);
+  rc = ensure_lds_attr(d.device, fn);
+  if (rc) return rc;
+  const int64_t grid = (rows + p.R - 1) / p.R;
   if (grid > 0x7fffffff) return fail(TI_ERR_INVALID, "too many rows for one launch");
-  occ_note(fn, R, lds);
-  hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(grid)), dim3(R), lds, stream, a);
+  if (p.block != p.R && p.block > 512) return fail(TI_ERR_UNSUPPORTED, "two-lane walk needs tiles of <= 256 rows");
+  occ_note(fn, p.block, p.lds);
+  hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(grid)), dim3(p.block), p.lds, stream, p.a);
   TI_HIP(hipGetLastError());
   return TI_OK;
 }
@@ -3646,9 +3562,8 @@ int ti_forest_get_info(const ti_forest* f, ti_forest_info* info) {
                    : (f->layout == 7 || f->layout == 9) ? f->lx_ilp : 0;
   info->n_stages = (f->layout == 7 || f->layout == 9) && !f->h_lx_stage.empty()
                        ? static_cast<int32_t>(f->h_lx_stage.size() - 1) : 0;
-  if (f->layout == 10) {   // the stages of a float32 batch (launch sizes them the same way)
-    const size_t fixed = align16(static_cast<size_t>(pf->F) * pf->rows32 * 4) + 16;
-    const int64_t S = heap_stage_trees(pf, pf->stride32, fixed, pf->rows32);
+  if (f->layout == 10) {   // the stages of a float32 batch, as plan_launch sizes them
+    const int64_t S = heap_stage_trees(pf, TI_F32);
     info->n_stages = S > 0 ? static_cast<int32_t>((pf->T + S - 1) / S) : 0;
   }
   info->top_depth = (f->layout == 8 || f->layout == 9) ? f->hx_top : 0;

@@ -180,21 +180,7 @@ __global__ void __launch_bounds__(512) cheap_predict_kernel(const KArgs a) {
   finish_row<ACC, KMAX>(acc, a, row);
 }
 
-using CheapKernelFn = void (*)(KArgs);
-
-template <typename XT, typename ACC, bool XGB>
-CheapKernelFn select_cheap(int K, bool z) {
-  if constexpr (sizeof(ACC) == 8) {   // the LightGBM zero rule: float64 sums only
-    if (z) return K == 1 ? cheap_predict_kernel<XT, ACC, 1, true, XGB>
-                : K <= 4 ? cheap_predict_kernel<XT, ACC, 4, true, XGB>
-                         : cheap_predict_kernel<XT, ACC, 16, true, XGB>;
-  }
-  return K == 1 ? cheap_predict_kernel<XT, ACC, 1, false, XGB>
-       : K <= 4 ? cheap_predict_kernel<XT, ACC, 4, false, XGB>
-                : cheap_predict_kernel<XT, ACC, 16, false, XGB>;
-}
-
-// instantiated in treeinfer_k_cat.hip; xgb: the rule of the forest's categorical nodes
-CheapKernelFn kernels_cat(bool x64, bool acc64, int K, bool z, bool xgb);
+// instantiated in treeinfer_k_cat.hip, selected like every other walk
+// (treeinfer_dispatch.h: Walk::CatHeapXgb / CatHeapLgb)
 
 }  // namespace ti

@@ -1,7 +1,15 @@
-// treeinfer_dispatch.h — kernel selection across the per-type translation
-// units.  Each treeinfer_k_<x><a>.hip instantiates every kernel of one
-// (input type, accumulator type) pair, so the four compile in parallel.
+// treeinfer_dispatch.h — kernel selection across the translation units.  Each
+// treeinfer_k_<x><a>.hip instantiates every kernel of one (input type,
+// accumulator type) pair and treeinfer_k_cat.hip the categorical heap's for
+// all four pairs, so the five compile in parallel.
+//
+// The host names what it launches with a KernelKey; ti::select(key) is the one
+// way from a key to a kernel.  Each rule that turns a runtime value into a
+// template argument (K buckets, the zero rule, ILP rounding, prefetch depth,
+// group count) is written once below, at the walk it belongs to.
 #pragma once
+
+#include <type_traits>
 
 #include "treeinfer_kernels.h"
 
@@ -9,126 +17,142 @@ namespace ti {
 
 using KernelFn = void (*)(KArgs);
 
-// layout: 0 heap, 1 explicit, 3 binned heap, 6 record explicit, 7 staged
-// record explicit, 8 heap top + record bottom, 9 heap top + staged record
-// bottom (2, 4 and 5 were retired in round 3); 10 selects the fixed-layout
-// walk of layout 3 (bheap_fix_kernel), 11 layout 9's compact u8 bottom, 12
-// its compact u16 bottom, 13 the u16 bottom walked two lanes a row.  (These
-// ids are this header's own: the public layout 10 of ti_forest_info, the
-// categorical heap, has its kernels and selection in treeinfer_cheap.h.)
-// fl: feature image in
-// LDS; z: LightGBM zero rule; b16 / pf: binned heap (and layout 9) bin width
-// and prefetch depth.
-template <typename XT, typename ACC, int KMAX, bool B8>
-KernelFn select_tx(bool z, int pf) {
+// What a launch walks.  The number is the public layout (ti_forest_info) that
+// reaches it; 2, 4 and 5 were retired in round 3.
+enum class Walk {
+  Heap,             // 0: float heap                      heap_predict_kernel
+  Explicit,         // 1: float explicit                  explicit_predict_kernel
+  BinHeap,          // 3: binned heap, indexed walk       bheap_predict_kernel
+  BinHeapFixed,     // 3: binned heap, fixed-layout walk  bheap_fix_kernel
+  Record,           // 6: record explicit                 rexplicit_predict_kernel
+  StagedRecord,     // 7: staged record explicit          lexplicit_predict_kernel
+  HeapTopRecord,    // 8: heap top + record bottom        hexplicit_predict_kernel
+  HeapTopStaged,    // 9: heap top + staged record bottom texplicit_predict_kernel
+  BottomU8,         // 9: its compact u8 bottom           t8explicit_predict_kernel
+  BottomU16,        // 9: its compact u16 bottom          t16explicit_predict_kernel
+  BottomU16Split,   // 9: the u16 bottom, two lanes a row t16split_predict_kernel
+  CatHeapXgb,       // 10: categorical heap, XGBoost's rule   cheap_predict_kernel
+  CatHeapLgb,       // 10: categorical heap, LightGBM's rule  (treeinfer_cheap.h)
+};
+
+struct KernelKey {
+  Walk walk;
+  bool x64, acc64;   // float64 input / sums (else float32)
+  int K;             // output groups
+  bool feat_lds;     // Heap, Explicit: feature image in LDS
+  bool zero_rule;    // LightGBM zero rule (no binned heap walk has one)
+  bool bins16;       // BinHeap, BinHeapFixed, HeapTopStaged: u16 bins (else u8)
+  int ilp;           // record walks and bottoms: trees a lane walks at once
+  int prefetch;      // BinHeap: prefetch depth
+  int groups;        // BinHeapFixed: groups of 4 trees a stage (NG)
+};
+
+// A rule calls `f` with the template argument it chose, as an
+// integral_constant: f(Int<8>{}) -> kernel<..., 8>.
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+// K buckets to 1 / 4 / 16.  The LightGBM zero rule selects a ZERO kernel only
+// when the sums are float64; with float32 sums it is ignored.
+template <typename ACC, typename F>
+KernelFn with_k_zero(const KernelKey& k, F f) {
   if constexpr (sizeof(ACC) == 8) {
-    if (z) return pf >= 8 ? texplicit_predict_kernel<XT, ACC, KMAX, true, 8, B8>
-                  : pf == 7 ? texplicit_predict_kernel<XT, ACC, KMAX, true, 7, B8>
-                            : texplicit_predict_kernel<XT, ACC, KMAX, true, 4, B8>;
+    if (k.zero_rule)
+      return k.K == 1 ? f(Int<1>{}, std::true_type{})
+           : k.K <= 4 ? f(Int<4>{}, std::true_type{}) : f(Int<16>{}, std::true_type{});
   }
-  return pf >= 8 ? texplicit_predict_kernel<XT, ACC, KMAX, false, 8, B8>
-         : pf == 7 ? texplicit_predict_kernel<XT, ACC, KMAX, false, 7, B8>
-                   : texplicit_predict_kernel<XT, ACC, KMAX, false, 4, B8>;
+  return k.K == 1 ? f(Int<1>{}, std::false_type{})
+       : k.K <= 4 ? f(Int<4>{}, std::false_type{}) : f(Int<16>{}, std::false_type{});
 }
 
-template <typename XT, typename ACC, int KMAX>
-KernelFn select_layout(int layout, bool fl, bool z, bool b16, int pf) {
-  if (layout == 11) {   // layout 9 with the compact u8 bottom; pf carries the tree ILP
-    if constexpr (sizeof(ACC) == 8) {
-      if (z) return pf >= 8 ? t8explicit_predict_kernel<XT, ACC, KMAX, true, 8>
-                    : pf == 7 ? t8explicit_predict_kernel<XT, ACC, KMAX, true, 7>
-                              : t8explicit_predict_kernel<XT, ACC, KMAX, true, 4>;
-    }
-    return pf >= 8 ? t8explicit_predict_kernel<XT, ACC, KMAX, false, 8>
-           : pf == 7 ? t8explicit_predict_kernel<XT, ACC, KMAX, false, 7>
-                     : t8explicit_predict_kernel<XT, ACC, KMAX, false, 4>;
-  }
-  if (layout == 13) {   // the compact u16 bottom, two lanes a row: 4 trees a lane (8 a group)
-    if constexpr (sizeof(ACC) == 8) {
-      if (z) return t16split_predict_kernel<XT, ACC, KMAX, true, 4>;
-    }
-    return t16split_predict_kernel<XT, ACC, KMAX, false, 4>;
-  }
-  if (layout == 12) {   // layout 9 with the compact u16 bottom; pf carries the tree ILP
-    if constexpr (sizeof(ACC) == 8) {
-      if (z) return pf >= 8 ? t16explicit_predict_kernel<XT, ACC, KMAX, true, 8>
-                            : t16explicit_predict_kernel<XT, ACC, KMAX, true, 4>;
-    }
-    return pf >= 8 ? t16explicit_predict_kernel<XT, ACC, KMAX, false, 8>
-                   : t16explicit_predict_kernel<XT, ACC, KMAX, false, 4>;
-  }
-  if (layout == 9) {   // pf carries the tree ILP (4, 7 or 8); b16 false: u8 bins
-    if (!b16) return select_tx<XT, ACC, KMAX, true>(z, pf);
-    return select_tx<XT, ACC, KMAX, false>(z, pf);
-  }
-  if (layout == 8) {   // pf carries the tree ILP (4 or 8)
-    if constexpr (sizeof(ACC) == 8) {
-      if (z) return pf >= 8 ? hexplicit_predict_kernel<XT, ACC, KMAX, true, 8>
-                            : hexplicit_predict_kernel<XT, ACC, KMAX, true, 4>;
-    }
-    return pf >= 8 ? hexplicit_predict_kernel<XT, ACC, KMAX, false, 8>
-                   : hexplicit_predict_kernel<XT, ACC, KMAX, false, 4>;
-  }
-  if (layout == 7) {   // pf carries the tree ILP (4, 7 or 8: about a stage's trees)
-    if constexpr (sizeof(ACC) == 8) {
-      if (z) return pf >= 8 ? lexplicit_predict_kernel<XT, ACC, KMAX, true, 8>
-                    : pf == 7 ? lexplicit_predict_kernel<XT, ACC, KMAX, true, 7>
-                              : lexplicit_predict_kernel<XT, ACC, KMAX, true, 4>;
-    }
-    return pf >= 8 ? lexplicit_predict_kernel<XT, ACC, KMAX, false, 8>
-           : pf == 7 ? lexplicit_predict_kernel<XT, ACC, KMAX, false, 7>
-                     : lexplicit_predict_kernel<XT, ACC, KMAX, false, 4>;
-  }
-  if (layout == 6) {   // pf carries the tree ILP (4, 8 or 16)
-    if constexpr (sizeof(ACC) == 8) {
-      if (z) {
-        if (pf >= 16) return rexplicit_predict_kernel<XT, ACC, KMAX, true, 16>;
-        if (pf >= 8) return rexplicit_predict_kernel<XT, ACC, KMAX, true, 8>;
-        return rexplicit_predict_kernel<XT, ACC, KMAX, true, 4>;
+// Tree ILP rounding.  Records take 16 / 8 / 4; the staged walks (about a
+// stage's trees) 8 / 7 / 4; the heap top and the u16 bottom 8 / 4, so 7 gives 4.
+template <typename F>
+KernelFn ilp_16_8_4(int ilp, F f) {
+  return ilp >= 16 ? f(Int<16>{}) : ilp >= 8 ? f(Int<8>{}) : f(Int<4>{});
+}
+template <typename F>
+KernelFn ilp_8_7_4(int ilp, F f) {
+  return ilp >= 8 ? f(Int<8>{}) : ilp == 7 ? f(Int<7>{}) : f(Int<4>{});
+}
+template <typename F>
+KernelFn ilp_8_4(int ilp, F f) {
+  return ilp >= 8 ? f(Int<8>{}) : f(Int<4>{});
+}
+
+template <typename XT, typename ACC, int KMAX, bool ZERO>
+KernelFn select_walk(const KernelKey& k) {
+  switch (k.walk) {
+    case Walk::Heap:
+      return k.feat_lds ? heap_predict_kernel<XT, ACC, KMAX, true, ZERO>
+                        : heap_predict_kernel<XT, ACC, KMAX, false, ZERO>;
+    case Walk::Explicit:
+      return k.feat_lds ? explicit_predict_kernel<XT, ACC, KMAX, true, ZERO>
+                        : explicit_predict_kernel<XT, ACC, KMAX, false, ZERO>;
+    case Walk::BinHeap:   // prefetch depth 4 up to 4, else 8
+      if (k.bins16) return k.prefetch <= 4 ? bheap_predict_kernel<XT, ACC, KMAX, true, 4>
+                                           : bheap_predict_kernel<XT, ACC, KMAX, true, 8>;
+      return k.prefetch <= 4 ? bheap_predict_kernel<XT, ACC, KMAX, false, 4>
+                             : bheap_predict_kernel<XT, ACC, KMAX, false, 8>;
+    case Walk::BinHeapFixed:   // float X, float sums only; NG 2 from 2 up, else 1
+      if constexpr (sizeof(XT) == 4 && sizeof(ACC) == 4) {
+        if (k.bins16) return k.groups >= 2 ? bheap_fix_kernel<XT, KMAX, true, 2>
+                                           : bheap_fix_kernel<XT, KMAX, true, 1>;
+        return k.groups >= 2 ? bheap_fix_kernel<XT, KMAX, false, 2>
+                             : bheap_fix_kernel<XT, KMAX, false, 1>;
       }
-    }
-    if (pf >= 16) return rexplicit_predict_kernel<XT, ACC, KMAX, false, 16>;
-    if (pf >= 8) return rexplicit_predict_kernel<XT, ACC, KMAX, false, 8>;
-    return rexplicit_predict_kernel<XT, ACC, KMAX, false, 4>;
+      return nullptr;
+    case Walk::Record:
+      return ilp_16_8_4(k.ilp, [](auto I) -> KernelFn {
+        return rexplicit_predict_kernel<XT, ACC, KMAX, ZERO, decltype(I)::value>;
+      });
+    case Walk::StagedRecord:
+      return ilp_8_7_4(k.ilp, [](auto I) -> KernelFn {
+        return lexplicit_predict_kernel<XT, ACC, KMAX, ZERO, decltype(I)::value>;
+      });
+    case Walk::HeapTopRecord:
+      return ilp_8_4(k.ilp, [](auto I) -> KernelFn {
+        return hexplicit_predict_kernel<XT, ACC, KMAX, ZERO, decltype(I)::value>;
+      });
+    case Walk::HeapTopStaged:   // last argument B8: u8 bins
+      return ilp_8_7_4(k.ilp, [&k](auto I) -> KernelFn {
+        return k.bins16 ? texplicit_predict_kernel<XT, ACC, KMAX, ZERO, decltype(I)::value, false>
+                        : texplicit_predict_kernel<XT, ACC, KMAX, ZERO, decltype(I)::value, true>;
+      });
+    case Walk::BottomU8:
+      return ilp_8_7_4(k.ilp, [](auto I) -> KernelFn {
+        return t8explicit_predict_kernel<XT, ACC, KMAX, ZERO, decltype(I)::value>;
+      });
+    case Walk::BottomU16:
+      return ilp_8_4(k.ilp, [](auto I) -> KernelFn {
+        return t16explicit_predict_kernel<XT, ACC, KMAX, ZERO, decltype(I)::value>;
+      });
+    case Walk::BottomU16Split:   // always 4 trees a lane (8 a group)
+      return t16split_predict_kernel<XT, ACC, KMAX, ZERO, 4>;
+    case Walk::CatHeapXgb:
+    case Walk::CatHeapLgb:
+      break;   // kernels_cat
   }
-  if (layout == 10) {   // binned heap, fixed layout: float X, float sums; pf carries NG
-    if constexpr (sizeof(XT) == 4 && sizeof(ACC) == 4) {
-      if (b16) return pf >= 2 ? bheap_fix_kernel<XT, KMAX, true, 2> : bheap_fix_kernel<XT, KMAX, true, 1>;
-      return pf >= 2 ? bheap_fix_kernel<XT, KMAX, false, 2> : bheap_fix_kernel<XT, KMAX, false, 1>;
-    }
-    return nullptr;
-  }
-  if (layout == 3) {
-    if (b16) return pf <= 4 ? bheap_predict_kernel<XT, ACC, KMAX, true, 4>
-                            : bheap_predict_kernel<XT, ACC, KMAX, true, 8>;
-    return pf <= 4 ? bheap_predict_kernel<XT, ACC, KMAX, false, 4>
-                   : bheap_predict_kernel<XT, ACC, KMAX, false, 8>;
-  }
-  // the LightGBM zero rule exists only for float64-accumulating forests
-  if constexpr (sizeof(ACC) == 8) {
-    if (z) {
-      if (layout == 0) return fl ? heap_predict_kernel<XT, ACC, KMAX, true, true>
-                                 : heap_predict_kernel<XT, ACC, KMAX, false, true>;
-      return fl ? explicit_predict_kernel<XT, ACC, KMAX, true, true>
-                : explicit_predict_kernel<XT, ACC, KMAX, false, true>;
-    }
-  }
-  if (layout == 0) return fl ? heap_predict_kernel<XT, ACC, KMAX, true, false>
-                             : heap_predict_kernel<XT, ACC, KMAX, false, false>;
-  return fl ? explicit_predict_kernel<XT, ACC, KMAX, true, false>
-            : explicit_predict_kernel<XT, ACC, KMAX, false, false>;
+  return nullptr;
 }
 
 template <typename XT, typename ACC>
-KernelFn select_types(int layout, int K, bool fl, bool z, bool b16, int pf) {
-  if (K == 1) return select_layout<XT, ACC, 1>(layout, fl, z, b16, pf);
-  if (K <= 4) return select_layout<XT, ACC, 4>(layout, fl, z, b16, pf);
-  return select_layout<XT, ACC, 16>(layout, fl, z, b16, pf);
+KernelFn select_types(const KernelKey& k) {
+  return with_k_zero<ACC>(k, [&k](auto KM, auto Z) -> KernelFn {
+    return select_walk<XT, ACC, decltype(KM)::value, decltype(Z)::value>(k);
+  });
 }
 
-KernelFn kernels_ff(int layout, int K, bool fl, bool z, bool b16, int pf);   // float X, float acc
-KernelFn kernels_fd(int layout, int K, bool fl, bool z, bool b16, int pf);   // float X, double acc
-KernelFn kernels_dd(int layout, int K, bool fl, bool z, bool b16, int pf);   // double X, double acc
-KernelFn kernels_df(int layout, int K, bool fl, bool z, bool b16, int pf);   // double X, float acc
+KernelFn kernels_ff(const KernelKey& k);    // float X, float acc
+KernelFn kernels_fd(const KernelKey& k);    // float X, double acc
+KernelFn kernels_dd(const KernelKey& k);    // double X, double acc
+KernelFn kernels_df(const KernelKey& k);    // double X, float acc
+KernelFn kernels_cat(const KernelKey& k);   // the categorical heap, every pair
+
+inline KernelFn select(const KernelKey& k) {
+  if (k.walk == Walk::CatHeapXgb || k.walk == Walk::CatHeapLgb) return kernels_cat(k);
+  if (!k.x64) return k.acc64 ? kernels_fd(k) : kernels_ff(k);
+  return k.acc64 ? kernels_dd(k) : kernels_df(k);
+}
 
 }  // namespace ti

@@ -2,7 +2,5 @@
 #include "treeinfer_dispatch.h"
 
 namespace ti {
-KernelFn kernels_dd(int layout, int K, bool fl, bool z, bool b16, int pf) {
-  return select_types<double, double>(layout, K, fl, z, b16, pf);
-}
+KernelFn kernels_dd(const KernelKey& k) { return select_types<double, double>(k); }
 }  // namespace ti

@@ -2,7 +2,5 @@
 #include "treeinfer_dispatch.h"
 
 namespace ti {
-KernelFn kernels_fd(int layout, int K, bool fl, bool z, bool b16, int pf) {
-  return select_types<float, double>(layout, K, fl, z, b16, pf);
-}
+KernelFn kernels_fd(const KernelKey& k) { return select_types<float, double>(k); }
 }  // namespace ti

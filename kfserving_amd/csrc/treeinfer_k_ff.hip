@@ -2,7 +2,5 @@
 #include "treeinfer_dispatch.h"
 
 namespace ti {
-KernelFn kernels_ff(int layout, int K, bool fl, bool z, bool b16, int pf) {
-  return select_types<float, float>(layout, K, fl, z, b16, pf);
-}
+KernelFn kernels_ff(const KernelKey& k) { return select_types<float, float>(k); }
 }  // namespace ti
