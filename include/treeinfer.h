@@ -64,6 +64,23 @@
  *     sklearn  (f32 x <= f64 t): threshold = t, NAN_LEFT = missing_go_to_left
  *   For float32 inputs the library compares against round_down_f32(threshold),
  *   which is exact for every float32 x; float64 inputs compare in float64.
+ *
+ * Linear leaves (ABI 6; LightGBM >= 3.2 linear_tree=true, Tree::Predict with
+ * is_linear_): when desc.lin_offset is set, the leaf n a row reaches adds, in
+ * float64,
+ *     out = lin_const[n]
+ *     for i in lin_offset[n] .. lin_offset[n+1]-1, in order:
+ *         v = X[row, lin_feature[i]]     (the value the splits read: float32
+ *                                         widened exactly, lgb_zero_map applied,
+ *                                         a column >= n_cols reads NaN)
+ *         if v is NaN: the leaf adds leaf_value[n] instead (the partial sum
+ *                      is discarded)
+ *         out = out + lin_coeff[i] * v   (one multiply, then one add: never fused)
+ *   Only NaN falls back; +-inf propagates (0.0 * inf makes the score NaN).  A
+ *   constant tree inside a linear forest has empty ranges and lin_const =
+ *   leaf_value.  Needs leaf_width == 1, accum_dtype == TI_F64, at most 16
+ *   output groups, and leaf_id = 0 .. L-1 within each tree (LightGBM's).
+ *   TI_OUTPUT_CONTRIB of a linear forest is TI_ERR_UNSUPPORTED (fatal upstream).
  */
 #ifndef TREEINFER_H_
 #define TREEINFER_H_
@@ -74,7 +91,7 @@
 extern "C" {
 #endif
 
-#define TI_ABI_VERSION 5
+#define TI_ABI_VERSION 6
 
 /* return codes */
 #define TI_OK               0
@@ -156,6 +173,14 @@ typedef struct ti_forest_desc {
    * the model file has none -- TI_OUTPUT_CONTRIB is then unsupported.  Replaces
    * XGBoosterPredict(option_mask = pred_contribs) / LGBM predict_type = 3. */
   const double*  cover;       /* [N]                                                */
+  /* linear leaves (ABI 6); NULL / 0 when the forest has none.  CSR over the
+   * nodes, internal nodes own empty ranges.  Replaces leaf_const / leaf_features
+   * / leaf_coeff of a LightGBM tree (tree.h, model text v3 with is_linear=1). */
+  int64_t n_lin_terms;        /* M                                                  */
+  const int64_t* lin_offset;  /* [N+1] first term of node n's linear model          */
+  const int32_t* lin_feature; /* [M]   raw column of each term                      */
+  const double*  lin_coeff;   /* [M]   coefficient of each term                     */
+  const double*  lin_const;   /* [N]   constant of node n's linear model            */
 } ti_forest_desc;
 
 typedef struct ti_forest ti_forest;   /* opaque, owns device memory */
@@ -190,7 +215,7 @@ typedef struct ti_forest_info {
   int32_t shap_table;         /* 1 built, 0 not (yet) built, -1 not buildable: over
                                  TI_OPT_SHAP_TABLE_MB or its allocation failed; the
                                  extend / unwind kernel serves every batch          */
-  int32_t reserved1;
+  int32_t linear;             /* ABI 6: 1 the forest has linear leaves, 0 not        */
   int64_t shap_table_bytes;   /* device bytes of the built table                     */
   double  shap_table_build_ms;/* host wall time of the last table build             */
 } ti_forest_info;
@@ -212,6 +237,10 @@ typedef struct ti_forest_info {
                                      the staging chunks.  The caller must not
                                      predict concurrently into buffers sharing a
                                      page with this call's.                         */
+#define TI_OPT_LINEAR_SCRATCH_MB 4 /* ABI 6, forests with linear leaves: MiB of leaf-id
+                                     scratch one pass over a row block may take
+                                     (DESIGN.md 3.5); a block is at least one tile
+                                     of rows (0: exactly one).  Default 1024.       */
 
 /* Upload the forest to each listed device (HIP device ordinals).  HIP is
  * initialised here, not at library load, so a process may fork before it.

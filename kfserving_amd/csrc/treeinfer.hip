@@ -35,6 +35,7 @@
 #include "treeinfer.h"
 #include "treeinfer_kernels.h"
 #include "treeinfer_dispatch.h"
+#include "treeinfer_linear.h"
 
 using ti::ExpNode;
 using ti::HeapNode;
@@ -575,6 +576,10 @@ struct DeviceForest {
   void* tx8_val = nullptr;       //   leaf value per bottom position (ACC)
   int32_t* tx8_ord = nullptr;    //   leaf ordinal per bottom position   // staged record layout (7): first tree of each stage
   uint32_t* hx_top[2] = {nullptr, nullptr};   // heap tops of layout 8, per input dtype
+  // linear leaves (treeinfer_linear.h): leaf records, their terms, first record of each tree
+  ti::LinLeaf* lin_leaves = nullptr;
+  ti::LinTerm* lin_terms = nullptr;
+  int64_t* lin_leaf_base = nullptr;
   // TreeSHAP path tables
   ShapPath* shap_paths = nullptr;
   ShapElem* shap_elems = nullptr;
@@ -716,6 +721,14 @@ struct ti_forest {
   int32_t has_cat = 0;       // some split is categorical ...
   int32_t has_cat_xgb = 0;   // ... with XGBoost's rule (TI_NODE_CAT_XGB)
   int32_t has_cat_lgb = 0;   // ... with LightGBM's rule
+  // linear leaves (ABI 6): per tree the first leaf record, per (tree, library
+  // leaf id) a record, per term a 16-byte {coefficient, feature}; kept on the
+  // host (every replica uploads them).  lin_scratch_mb: TI_OPT_LINEAR_SCRATCH_MB
+  int32_t linear = 0;
+  std::vector<ti::LinLeaf> h_lin_leaves;
+  std::vector<ti::LinTerm> h_lin_terms;
+  std::vector<int64_t> h_lin_leaf_base;
+  std::atomic<int64_t> lin_scratch_mb{1024};
   std::vector<unsigned char> h_leaves;   // ACC-typed
   std::vector<std::unique_ptr<DeviceForest>> devs;
 };
@@ -743,7 +756,7 @@ void free_device(DeviceForest& d) {
                   d.shap_paths, d.shap_elems, d.shap_leaf, d.shap_bias, d.shap_tab, d.shap_tab_off,
                   d.rx_recs[0], d.rx_recs[1], d.rx_base, d.rx_nint, d.lx_stage,
                   d.tx8_pos, d.tx8_val, d.tx8_ord,
-                  d.hx_top[0], d.hx_top[1]};
+                  d.hx_top[0], d.hx_top[1], d.lin_leaves, d.lin_terms, d.lin_leaf_base};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (d.hx_pin) (void)hipHostFree(d.hx_pin);
@@ -777,6 +790,9 @@ void free_device(DeviceForest& d) {
   d.tx8_val = nullptr;
   d.tx8_ord = nullptr;
   d.hx_top[0] = d.hx_top[1] = nullptr;
+  d.lin_leaves = nullptr;
+  d.lin_terms = nullptr;
+  d.lin_leaf_base = nullptr;
   d.shap_paths = nullptr;
   d.shap_elems = nullptr;
   d.shap_leaf = d.shap_bias = nullptr;
@@ -823,6 +839,29 @@ int validate(const ti_forest_desc* d, std::vector<int>* depth_out) {
   if (d->leaf_width == 1 && !d->tree_group) return fail(TI_ERR_INVALID, "null tree_group");
   if (d->tree_offset[0] != 0 || d->tree_offset[d->n_trees] != d->n_nodes)
     return fail(TI_ERR_INVALID, "tree_offset must start at 0 and end at n_nodes");
+  if (d->lin_offset) {   // linear leaves (ABI 6)
+    if (d->leaf_width != 1)
+      return fail(TI_ERR_INVALID, "linear leaves need leaf_width == 1");
+    if (d->accum_dtype != TI_F64)
+      return fail(TI_ERR_INVALID, "linear leaves need float64 sums (accum_dtype TI_F64)");
+    if (!d->lin_const) return fail(TI_ERR_INVALID, "linear leaves without lin_const");
+    if (d->n_lin_terms < 0 || d->n_lin_terms > 0xffffffffLL)
+      return fail(TI_ERR_INVALID, "n_lin_terms out of range");
+    if (d->n_lin_terms > 0 && (!d->lin_feature || !d->lin_coeff))
+      return fail(TI_ERR_INVALID, "linear terms without lin_feature / lin_coeff");
+    if (d->lin_offset[0] != 0 || d->lin_offset[d->n_nodes] != d->n_lin_terms)
+      return fail(TI_ERR_INVALID, "lin_offset must start at 0 and end at n_lin_terms");
+    for (int64_t n = 0; n < d->n_nodes; ++n)
+      if (d->lin_offset[n + 1] < d->lin_offset[n])
+        return fail(TI_ERR_INVALID, "lin_offset must not decrease");
+    for (int64_t i = 0; i < d->n_lin_terms; ++i)
+      if (d->lin_feature[i] < 0 || d->lin_feature[i] >= d->n_features)
+        return fail(TI_ERR_INVALID, "lin_feature out of [0, n_features)");
+    if (d->n_groups > ti::kMaxGroups)
+      return fail(TI_ERR_UNSUPPORTED,
+                  "linear leaves with more than 16 output groups: such forests are split into "
+                  "group parts, and the linear tables are not subset per part");
+  }
   depth_out->assign(d->n_trees, 0);
   std::vector<int> stack_node, stack_depth;
   for (int t = 0; t < d->n_trees; ++t) {
@@ -2149,6 +2188,11 @@ int upload_device(ti_forest* f, DeviceForest& d, int device) {
     if ((rc = upload(&d.exp_leaf_ids, f->h_exp_leaf_ids, &d.bytes))) return rc;
     if ((rc = upload(&d.cat_words, f->h_cat_words, &d.bytes))) return rc;
   }
+  if (f->linear) {
+    if ((rc = upload(&d.lin_leaves, f->h_lin_leaves, &d.bytes))) return rc;
+    if ((rc = upload(&d.lin_terms, f->h_lin_terms, &d.bytes))) return rc;
+    if ((rc = upload(&d.lin_leaf_base, f->h_lin_leaf_base, &d.bytes))) return rc;
+  }
   return TI_OK;
 }
 
@@ -3165,12 +3209,73 @@ int launch_contrib(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_
   return TI_OK;
 }
 
+// Linear leaves: two stream-ordered passes per row block.  Pass 1 is the
+// forest's own walk with TI_OUTPUT_LEAF into a [rows_block, T] int32 scratch;
+// pass 2 (linear_leaf_kernel) evaluates each reached leaf's linear model on
+// the raw features and finishes the row.  A block is as many whole tiles of
+// pass 2 as fit TI_OPT_LINEAR_SCRATCH_MB, at least one.
+int launch_linear(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows, int32_t cols,
+                  int64_t stride, int kind, void* out, hipStream_t stream) {
+  if (rows <= 0) return TI_OK;
+  const size_t xs = dtype_size(xdt);
+  // TI_LINEAR_FEAT_LDS=0 (developer knob): features from HBM even where the image fits (an A/B)
+  const int R = env_int("TI_LINEAR_FEAT_LDS", 1) != 0 ? pick_rows(f->F, xs, 0) : 0;   // 0: HBM
+  const bool feat_lds = R > 0;
+  const int block = feat_lds ? R : 256;
+  const size_t lds = (feat_lds ? align16(static_cast<size_t>(f->F) * block * xs) : 0) + 16 +
+                     static_cast<size_t>(block) * ti::kLinPitch * 4;
+  LaunchPlan p;   // the shared prologue's and epilogue's arguments, as every walk gets them
+  int rc = plan_launch(f, d, xdt, kind, &p);
+  if (rc) return rc;
+  ti::LinearFn fn = xdt == TI_F64 ? ti::select_linear<double>(f->K, feat_lds)
+                                  : ti::select_linear<float>(f->K, feat_lds);
+  rc = ensure_lds_attr(d.device, reinterpret_cast<KernelFn>(fn));
+  if (rc) return rc;
+  const int64_t row_bytes = static_cast<int64_t>(4) * f->T;
+  int64_t rows_block = (f->lin_scratch_mb.load() << 20) / row_bytes;
+  rows_block = std::max<int64_t>(block, rows_block / block * block);
+  rows_block = std::min(rows_block, (rows + block - 1) / block * block);
+  int32_t* ids = nullptr;
+  if (hipMallocAsync(reinterpret_cast<void**>(&ids),
+                     static_cast<size_t>(std::min(rows, rows_block) * row_bytes), stream) != hipSuccess)
+    return fail(TI_ERR_NOMEM, "leaf-id scratch allocation failed");
+  const size_t out_row = static_cast<size_t>(output_width(f, kind)) * 8;
+  for (int64_t r0 = 0; r0 < rows && rc == TI_OK; r0 += rows_block) {
+    const int64_t nb = std::min(rows_block, rows - r0);
+    const void* xb = static_cast<const unsigned char*>(X) + static_cast<size_t>(r0 * stride) * xs;
+    rc = launch(f, d, xb, xdt, nb, cols, stride, TI_OUTPUT_LEAF, ids, stream);
+    if (rc) break;
+    KArgs a = p.a;
+    a.X = xb;
+    a.n_rows = nb;
+    a.row_stride = stride;
+    a.n_cols = cols;
+    a.out = static_cast<unsigned char*>(out) + static_cast<size_t>(r0) * out_row;
+    ti::LinArgs la;
+    la.leaf_ids = ids;
+    la.leaves = d.lin_leaves;
+    la.terms = d.lin_terms;
+    la.leaf_base = d.lin_leaf_base;
+    hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>((nb + block - 1) / block)), dim3(block), lds,
+                       stream, a, la);
+    if (hipGetLastError() != hipSuccess) rc = fail(TI_ERR_DEVICE, "linear leaf launch failed");
+  }
+  (void)hipFreeAsync(ids, stream);
+  return rc;
+}
+
 int launch_any(ti_forest* f, int slot, const void* X, int xdt, int64_t rows, int32_t cols,
                int64_t stride, int kind, void* out, hipStream_t stream) {
+  if (kind == TI_OUTPUT_CONTRIB && f->linear)
+    return fail(TI_ERR_UNSUPPORTED,
+                "TI_OUTPUT_CONTRIB of a forest with linear leaves (LightGBM itself refuses "
+                "pred_contrib on a linear-tree model)");
   if (kind == TI_OUTPUT_CONTRIB && f->parts.empty())
     return launch_contrib(f, *f->devs[slot], X, xdt, rows, cols, stride, out, stream);
   if (!f->parts.empty())
     return launch_chunked(f, slot, X, xdt, rows, cols, stride, kind, out, stream);
+  if (f->linear && (kind == TI_OUTPUT_MARGIN || kind == TI_OUTPUT_PREDICT))
+    return launch_linear(f, *f->devs[slot], X, xdt, rows, cols, stride, kind, out, stream);
   return launch(f, *f->devs[slot], X, xdt, rows, cols, stride, kind, out, stream);
 }
 
@@ -3297,6 +3402,45 @@ bool plan_cheap(const ti_forest_desc* desc, ti_forest* f, int D, bool forced) {
     pack_cheap<double, float>(desc, D, s64, sc64, &f->h_heap64, nullptr);
   }
   return true;
+}
+
+// Linear leaves: a record per (tree, library leaf id) -- what TI_OUTPUT_LEAF
+// reports is what pass 2 indexes -- and the terms as 16-byte records.
+int pack_linear(const ti_forest_desc* d, ti_forest* f) {
+  f->h_lin_leaf_base.assign(d->n_trees, 0);
+  f->h_lin_terms.resize(static_cast<size_t>(d->n_lin_terms));
+  for (int64_t i = 0; i < d->n_lin_terms; ++i) {
+    ti::LinTerm& t = f->h_lin_terms[i];
+    t.coeff = d->lin_coeff[i];
+    t.feature = static_cast<uint32_t>(d->lin_feature[i]);
+    t.pad = 0;
+  }
+  std::vector<char> seen;
+  for (int t = 0; t < d->n_trees; ++t) {
+    const int64_t b = d->tree_offset[t], e = d->tree_offset[t + 1];
+    int64_t nl = 0;
+    for (int64_t g = b; g < e; ++g) nl += d->feature[g] < 0;
+    const size_t base = f->h_lin_leaves.size();
+    f->h_lin_leaf_base[t] = static_cast<int64_t>(base);
+    f->h_lin_leaves.resize(base + static_cast<size_t>(nl));
+    seen.assign(static_cast<size_t>(nl), 0);
+    for (int64_t g = b; g < e; ++g) {
+      if (d->feature[g] >= 0) continue;
+      const int64_t id = d->leaf_id[g];
+      if (id < 0 || id >= nl || seen[id])
+        return fail(TI_ERR_INVALID, "linear leaves need leaf_id = 0 .. L-1 within tree " +
+                                        std::to_string(t));
+      seen[id] = 1;
+      ti::LinLeaf& l = f->h_lin_leaves[base + static_cast<size_t>(id)];
+      l.lconst = d->lin_const[g];
+      l.fallback = d->leaf_value[g];
+      l.begin = static_cast<uint32_t>(d->lin_offset[g]);
+      l.count = static_cast<uint32_t>(d->lin_offset[g + 1] - d->lin_offset[g]);
+      l.pad[0] = l.pad[1] = 0;
+    }
+  }
+  f->linear = 1;
+  return TI_OK;
 }
 
 // The forest whose DeviceForest (stream, staging buffers, lock) serves a slot.
@@ -3485,6 +3629,10 @@ int ti_forest_create(const ti_forest_desc* desc, const int32_t* devices, int32_t
       }
     }
   }
+  if (desc->lin_offset) {
+    rc = pack_linear(desc, f.get());
+    if (rc) return rc;
+  }
   keep_shap_source(desc, f.get());
   for (int i = 0; i < n_devices; ++i) {
     f->devs.emplace_back(new DeviceForest());
@@ -3571,7 +3719,7 @@ int ti_forest_get_info(const ti_forest* f, ti_forest_info* info) {
   // the TreeSHAP coefficient table of slot 0 (of the first part)
   const ti_forest* sf = f->parts.empty() ? f : f->parts[0].get();
   info->shap_table = sf->devs.empty() ? 0 : sf->devs[0]->shap_tab_state.load();
-  info->reserved1 = 0;
+  info->linear = f->linear;
   info->shap_table_bytes = info->shap_table == 1 ? sf->shap_tab_len * sf->shap_tab_mt : 0;
   info->shap_table_build_ms = sf->shap_tab_build_ms;
   return TI_OK;
@@ -3596,6 +3744,10 @@ int ti_forest_set_option(ti_forest* f, int32_t option, int64_t value) {
     case TI_OPT_HOST_REGISTER:
       if (value != 0 && value != 1) return fail(TI_ERR_INVALID, "TI_OPT_HOST_REGISTER must be 0 or 1");
       f->host_register.store(static_cast<int32_t>(value));
+      return TI_OK;
+    case TI_OPT_LINEAR_SCRATCH_MB:
+      if (value < 0) return fail(TI_ERR_INVALID, "TI_OPT_LINEAR_SCRATCH_MB must be >= 0");
+      f->lin_scratch_mb.store(std::min<int64_t>(value, int64_t(1) << 30));
       return TI_OK;
     default:
       return fail(TI_ERR_INVALID, "unknown option " + std::to_string(option));

@@ -21,7 +21,7 @@ import numpy as np
 from .forest import (Forest, OUT_CONTRIB, OUT_LEAF, OUT_MARGIN, OUT_PREDICT, TI_F32, TI_F64,
                      TI_I32)
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 _LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("TREEINFER_LIB", os.path.join(_LIB_DIR, "libtreeinfer.so"))
 
@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = (
 OPT_SHAP_TABLE_ROWS = 1
 OPT_SHAP_TABLE_MB = 2
 OPT_HOST_REGISTER = 3
+OPT_LINEAR_SCRATCH_MB = 4
 
 
 class TreeInferError(RuntimeError):
@@ -75,6 +76,11 @@ class _ForestDesc(ctypes.Structure):
         ("cat_offset", ctypes.c_void_p),
         ("cat_nwords", ctypes.c_void_p),
         ("cover", ctypes.c_void_p),
+        ("n_lin_terms", ctypes.c_int64),
+        ("lin_offset", ctypes.c_void_p),
+        ("lin_feature", ctypes.c_void_p),
+        ("lin_coeff", ctypes.c_void_p),
+        ("lin_const", ctypes.c_void_p),
     ]
 
 
@@ -95,7 +101,7 @@ class _ForestInfo(ctypes.Structure):
         ("top_depth", ctypes.c_int32),
         ("bottom", ctypes.c_int32),
         ("shap_table", ctypes.c_int32),
-        ("reserved1", ctypes.c_int32),
+        ("linear", ctypes.c_int32),
         ("shap_table_bytes", ctypes.c_int64),
         ("shap_table_build_ms", ctypes.c_double),
     ]
@@ -231,6 +237,12 @@ class DeviceForest:
             desc.cat_nwords = _ptr(f.cat_nwords)
         if f.cover is not None:
             desc.cover = _ptr(f.cover)
+        if f.has_linear:
+            desc.n_lin_terms = int(f.lin_feature.shape[0])
+            desc.lin_offset = _ptr(f.lin_offset)
+            desc.lin_feature = _ptr(f.lin_feature) if f.lin_feature.size else None
+            desc.lin_coeff = _ptr(f.lin_coeff) if f.lin_coeff.size else None
+            desc.lin_const = _ptr(f.lin_const)
         dev_arr = (ctypes.c_int32 * len(devs))(*devs)
         handle = ctypes.c_void_p()
         _check(self._lib, self._lib.ti_forest_create(ctypes.byref(desc), dev_arr, len(devs),
@@ -245,8 +257,20 @@ class DeviceForest:
 
     def set_option(self, option: int, value: int) -> None:
         """ti_forest_set_option: speed knobs that never change results
-        (OPT_SHAP_TABLE_ROWS, OPT_SHAP_TABLE_MB, OPT_HOST_REGISTER)."""
+        (OPT_SHAP_TABLE_ROWS, OPT_SHAP_TABLE_MB, OPT_HOST_REGISTER,
+        OPT_LINEAR_SCRATCH_MB)."""
         _check(self._lib, self._lib.ti_forest_set_option(self._handle, option, int(value)))
+
+    def linear_tile_rows(self, x_dtype) -> int:
+        """Rows per tile of the linear-leaf pass (launch_linear in
+        treeinfer.hip) for input of ``x_dtype``: the largest of 256 / 128 / 64
+        whose [F][R] feature image fits 64 KiB of LDS, else 256 with the
+        features read from HBM.  Row blocks are whole tiles of this size."""
+        xs = np.dtype(x_dtype).itemsize
+        for r in (256, 128, 64):
+            if self.forest.n_features * r * xs <= 64 * 1024:
+                return r
+        return 256
 
     def output_shape(self, kind: int, n_rows: int):
         n = ctypes.c_int64()
@@ -300,6 +324,6 @@ class DeviceForest:
 
 
 __all__ = ["DeviceForest", "TreeInferError", "prepare_input", "load_library", "device_count", "default_devices",
-           "OPT_SHAP_TABLE_ROWS", "OPT_SHAP_TABLE_MB",
+           "OPT_SHAP_TABLE_ROWS", "OPT_SHAP_TABLE_MB", "OPT_HOST_REGISTER", "OPT_LINEAR_SCRATCH_MB",
            "EXPORTED_SYMBOLS", "OUT_MARGIN", "OUT_PREDICT", "OUT_LEAF", "OUT_CONTRIB", "TI_F32", "TI_F64",
            "TI_I32"]

@@ -94,6 +94,16 @@ class Forest:
     # node covers (xgboost sum_hess, LightGBM data counts, sklearn weighted
     # samples): the node weights of TreeSHAP contributions (OUT_CONTRIB)
     cover: Optional[np.ndarray] = None          # float64 [N]
+    # linear leaves (LightGBM linear_tree): CSR over the nodes, internal nodes
+    # own empty ranges.  The leaf n a row reaches adds lin_const[n] + sum of
+    # lin_coeff[i] * x[lin_feature[i]] over its range, or leaf_value[n] when
+    # one of those features is NaN (include/treeinfer.h).  All None when the
+    # forest has none; a constant tree inside a linear forest has empty
+    # ranges and lin_const = leaf_value
+    lin_offset: Optional[np.ndarray] = None     # int64 [N+1]
+    lin_feature: Optional[np.ndarray] = None    # int32 [M]
+    lin_coeff: Optional[np.ndarray] = None      # float64 [M]
+    lin_const: Optional[np.ndarray] = None      # float64 [N]
     library: str = ""
     objective: str = ""
     feature_names: Optional[List[str]] = None
@@ -106,6 +116,10 @@ class Forest:
     @property
     def n_nodes(self) -> int:
         return int(self.feature.shape[0])
+
+    @property
+    def has_linear(self) -> bool:
+        return self.lin_offset is not None
 
     def tree_slice(self, t: int) -> slice:
         return slice(int(self.tree_offset[t]), int(self.tree_offset[t + 1]))
@@ -165,6 +179,30 @@ class Forest:
             if np.any(self.cat_offset[cat] < 0) or np.any(end > self.cat_bits.shape[0]):
                 raise ValueError("categorical bitset out of range")
 
+        lin = (self.lin_offset, self.lin_feature, self.lin_coeff, self.lin_const)
+        if any(a is not None for a in lin):
+            if any(a is None for a in lin):
+                raise ValueError("linear leaves need lin_offset, lin_feature, lin_coeff and lin_const")
+            if self.leaf_width != 1:
+                raise ValueError("linear leaves need leaf_width == 1")
+            if self.accum_dtype != TI_F64:
+                raise ValueError("linear leaves need accum_dtype == TI_F64")
+            M = self.lin_feature.shape[0]
+            if self.lin_offset.shape[0] != N + 1:
+                raise ValueError(f"lin_offset has {self.lin_offset.shape[0]} entries, expected {N + 1}")
+            if self.lin_const.shape[0] != N:
+                raise ValueError(f"lin_const has {self.lin_const.shape[0]} entries, expected {N}")
+            if self.lin_coeff.shape[0] != M:
+                raise ValueError("lin_coeff and lin_feature differ in length")
+            if self.lin_offset[0] != 0 or self.lin_offset[-1] != M:
+                raise ValueError("lin_offset does not cover the term arrays")
+            if np.any(np.diff(self.lin_offset) < 0):
+                raise ValueError("lin_offset must not decrease")
+            if np.any(np.diff(self.lin_offset)[internal] != 0):
+                raise ValueError("internal nodes must own no linear terms")
+            if M and (self.lin_feature.min() < 0 or self.lin_feature.max() >= self.n_features):
+                raise ValueError("lin_feature outside [0, n_features)")
+
     def contiguous(self) -> "Forest":
         """Return self with every array C-contiguous in the ABI's dtypes."""
         self.tree_offset = np.ascontiguousarray(self.tree_offset, dtype=np.int64)
@@ -184,6 +222,11 @@ class Forest:
             self.cat_bits = np.ascontiguousarray(self.cat_bits, dtype=np.uint32)
             self.cat_offset = np.ascontiguousarray(self.cat_offset, dtype=np.int64)
             self.cat_nwords = np.ascontiguousarray(self.cat_nwords, dtype=np.int32)
+        if self.lin_offset is not None:
+            self.lin_offset = np.ascontiguousarray(self.lin_offset, dtype=np.int64)
+            self.lin_feature = np.ascontiguousarray(self.lin_feature, dtype=np.int32)
+            self.lin_coeff = np.ascontiguousarray(self.lin_coeff, dtype=np.float64)
+            self.lin_const = np.ascontiguousarray(self.lin_const, dtype=np.float64)
         return self
 
     def tree_subset(self, t0: int, t1: int, keep_base: bool = True) -> "Forest":
@@ -195,8 +238,15 @@ class Forest:
             raise ValueError(f"bad tree range [{t0}, {t1}) of {self.n_trees}")
         s = slice(int(self.tree_offset[t0]), int(self.tree_offset[t1]))
         cut = lambda a: None if a is None else np.ascontiguousarray(a[s])   # noqa: E731
+        lin = {}
+        if self.lin_offset is not None:   # the trees' terms, offsets rebased
+            m0, m1 = int(self.lin_offset[s.start]), int(self.lin_offset[s.stop])
+            lin = dict(lin_offset=self.lin_offset[s.start:s.stop + 1] - m0,
+                       lin_feature=np.ascontiguousarray(self.lin_feature[m0:m1]),
+                       lin_coeff=np.ascontiguousarray(self.lin_coeff[m0:m1]),
+                       lin_const=cut(self.lin_const))
         return dataclasses.replace(
-            self, tree_offset=self.tree_offset[t0:t1 + 1] - self.tree_offset[t0],
+            self, **lin, tree_offset=self.tree_offset[t0:t1 + 1] - self.tree_offset[t0],
             tree_group=np.ascontiguousarray(self.tree_group[t0:t1]),
             feature=cut(self.feature), threshold=cut(self.threshold), flags=cut(self.flags),
             left=cut(self.left), right=cut(self.right), leaf_id=cut(self.leaf_id),

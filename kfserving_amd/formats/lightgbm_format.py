@@ -17,6 +17,13 @@ node's threshold indexes ``cat_boundaries``; the row goes left iff bit
 ``(int)x`` is set in ``cat_threshold[cat_boundaries[c]:cat_boundaries[c+1]]``;
 NaN, negative and out-of-range values go right.  Bitsets are concatenated
 over the forest into ``Forest.cat_bits`` with per-node word offsets.
+
+Linear trees (``is_linear=1``, LightGBM >= 3.2 ``linear_tree=true``): a leaf
+holds ``leaf_const`` and ``num_features`` terms taken in order from the flat
+``leaf_features`` / ``leaf_coeff`` lists; it adds ``leaf_const + sum(coeff *
+x[feature])`` in float64, or ``leaf_value`` if one of those features is NaN.
+The terms become ``Forest.lin_*``, a CSR over the nodes; coefficients and
+constants are already shrunk in the file.
 """
 from __future__ import annotations
 
@@ -88,20 +95,55 @@ def _node_flags(decision_type: np.ndarray, threshold: np.ndarray) -> np.ndarray:
     return flags.astype(np.uint8)
 
 
+def _linear_leaves(block: Dict[str, str], num_leaves: int):
+    """The linear models of an ``is_linear=1`` block (Tree::ToString of
+    LightGBM >= 3.2): per-leaf constants, term counts, and the terms of all
+    leaves as two flat lists, ``num_features[j]`` tokens per leaf."""
+    try:
+        const = _floats(block.get("leaf_const", ""))
+        counts = _ints(block.get("num_features", ""))
+        feats = _ints(block.get("leaf_features", ""))
+        coeffs = _floats(block.get("leaf_coeff", ""))
+    except ValueError as e:
+        raise LightGBMFormatError(f"malformed linear tree: {e}") from None
+    if const.shape[0] != num_leaves:
+        raise LightGBMFormatError("leaf_const length != num_leaves")
+    if counts.shape[0] != num_leaves:
+        raise LightGBMFormatError("num_features length != num_leaves")
+    if np.any(counts < 0):
+        raise LightGBMFormatError("negative num_features")
+    total = int(counts.sum())
+    if feats.shape[0] != total:
+        raise LightGBMFormatError(f"leaf_features has {feats.shape[0]} tokens, expected {total}")
+    if coeffs.shape[0] != total:
+        raise LightGBMFormatError(f"leaf_coeff has {coeffs.shape[0]} tokens, expected {total}")
+    if np.any(feats < 0):
+        raise LightGBMFormatError("negative leaf_features index")
+    return const, counts, feats, coeffs
+
+
 def _tree(block: Dict[str, str]) -> dict:
     num_leaves = int(block["num_leaves"])
     leaf_value = _floats(block["leaf_value"])
     if leaf_value.shape[0] != num_leaves:
         raise LightGBMFormatError("leaf_value length != num_leaves")
+    n_int = num_leaves - 1
+    # per-node linear arrays: internal nodes own no terms; a constant tree is
+    # zero terms with lin_const = leaf_value (it needs no special case later)
+    lin = {"is_linear": False, "lin_count": np.zeros(n_int + num_leaves, dtype=np.int64),
+           "lin_const": np.concatenate([np.zeros(n_int), leaf_value]),
+           "lin_feature": np.zeros(0, dtype=np.int64), "lin_coeff": np.zeros(0)}
     if block.get("is_linear", "0").strip() not in ("", "0"):
-        raise LightGBMFormatError("linear trees are not supported")
+        const, counts, feats, coeffs = _linear_leaves(block, num_leaves)
+        lin = {"is_linear": True, "lin_count": np.concatenate([np.zeros(n_int, np.int64), counts]),
+               "lin_const": np.concatenate([np.zeros(n_int), const]),
+               "lin_feature": feats, "lin_coeff": coeffs}
     leaf_count = _floats(block["leaf_count"]) if "leaf_count" in block else None
     if num_leaves == 1:
         return {"feature": np.array([-1]), "threshold": np.zeros(1), "flags": np.zeros(1),
                 "left": np.array([-1]), "right": np.array([-1]), "leaf_id": np.array([0]),
                 "leaf_value": leaf_value.reshape(1, 1),
-                "cover": None if leaf_count is None else leaf_count[:1]}
-    n_int = num_leaves - 1
+                "cover": None if leaf_count is None else leaf_count[:1], **lin}
     feat = _ints(block["split_feature"])
     thr = _floats(block["threshold"])
     dt = _ints(block["decision_type"])
@@ -139,6 +181,7 @@ def _tree(block: Dict[str, str]) -> dict:
         # data counts (LightGBM's own SHAP weights children by them)
         "cover": (np.concatenate([_floats(block["internal_count"]), leaf_count])
                   if leaf_count is not None and "internal_count" in block else None),
+        **lin,
     }
 
 
@@ -187,12 +230,24 @@ def parse_lightgbm_text(text: str) -> Forest:
         cat_bits = np.concatenate(words).astype(np.uint32)
         cat_offset = np.concatenate(offs)
         cat_nwords = np.concatenate(nws).astype(np.int32)
+    # linear leaves: the trees' per-node term counts become one CSR over the
+    # forest's nodes (constant trees of a mixed model: zero terms each)
+    lin_offset, lin_feature, lin_coeff, lin_const = None, None, None, None
+    if any(t["is_linear"] for t in trees):
+        counts = np.concatenate([t["lin_count"] for t in trees])
+        lin_offset = np.zeros(counts.shape[0] + 1, dtype=np.int64)
+        np.cumsum(counts, out=lin_offset[1:])
+        lin_feature = np.concatenate([t["lin_feature"] for t in trees]).astype(np.int32)
+        lin_coeff = np.concatenate([t["lin_coeff"] for t in trees]).astype(np.float64)
+        lin_const = np.concatenate([t["lin_const"] for t in trees]).astype(np.float64)
     ntpi = int(header.get("num_tree_per_iteration", header.get("num_class", "1")))
     K = max(1, ntpi)
     n_features = int(header.get("max_feature_idx", "-1")) + 1
     used = cat["feature"][cat["feature"] >= 0]
     if used.size:
         n_features = max(n_features, int(used.max()) + 1)
+    if lin_feature is not None and lin_feature.size:
+        n_features = max(n_features, int(lin_feature.max()) + 1)
     objective = header.get("objective", "")
     transform, tparam = objective_transform(objective)
     average = "average_output" in flags_present or header.get("average_output") is not None
@@ -211,6 +266,7 @@ def parse_lightgbm_text(text: str) -> Forest:
         library="lightgbm", objective=objective, feature_names=names,
         meta={"version": header.get("version", ""), "num_class": int(header.get("num_class", 1))},
         cat_bits=cat_bits, cat_offset=cat_offset, cat_nwords=cat_nwords,
+        lin_offset=lin_offset, lin_feature=lin_feature, lin_coeff=lin_coeff, lin_const=lin_const,
     ).contiguous()
 
 
@@ -259,6 +315,17 @@ def write_lightgbm_text(path: str, trees: List[dict], n_features: int, objective
             out.append("leaf_count=" + " ".join(str(int(v)) for v in t["leaf_count"]))
             if nl > 1:
                 out.append("internal_count=" + " ".join(str(int(v)) for v in t["internal_count"]))
+        if "leaf_const" in t and "leaf_features" in t and "leaf_coeff" in t:
+            # Tree::ToString of a linear tree: each leaf's terms, then a blank,
+            # then one more blank -- a leaf without terms leaves only that one
+            def flat(per_leaf, fmt):
+                return "".join((" ".join(fmt(v) for v in leaf) + " " if len(leaf) else "") + " "
+                               for leaf in per_leaf)
+            out.append("is_linear=1")
+            out.append("leaf_const=" + " ".join(_fmt(v) for v in t["leaf_const"]))
+            out.append("num_features=" + " ".join(str(len(v)) for v in t["leaf_features"]))
+            out.append("leaf_features=" + flat(t["leaf_features"], lambda v: str(int(v))))
+            out.append("leaf_coeff=" + flat(t["leaf_coeff"], _fmt))
         out.append("shrinkage=1")
         out.append("")
         out.append("")
@@ -319,6 +386,40 @@ def add_categorical_splits(trees: List[dict], cat_features, n_categories: int, s
             t.update(split_feature=feat, threshold=thr, decision_type=dt,
                      cat_boundaries=np.asarray(bounds), cat_threshold=np.asarray(words))
     return trees
+
+
+def add_linear_leaves(trees: List[dict], n_features: int, seed: int, max_terms: int = 4,
+                      const_tree_every: int = 5) -> List[dict]:
+    """Give the leaves of ``trees`` linear models, the shape LightGBM writes
+    for ``linear_tree=true``: per leaf 0..``max_terms`` distinct features (the
+    count uniform, so some leaves have none), coefficients ~ N(0, 0.05^2) with
+    one in ten exactly 0.0, and a constant near the leaf's value.  Every ``const_tree_every``-th tree
+    (0, k, 2k, ...; 0: none) stays constant, so the model is mixed, as a
+    boosted model whose first tree is constant is.  Seeded; the trees' splits
+    and leaf values are unchanged."""
+    rng = np.random.default_rng([seed, 3203])
+    max_terms = min(int(max_terms), int(n_features))
+    for ti, t in enumerate(trees):
+        if const_tree_every > 0 and ti % const_tree_every == 0:
+            continue
+        lv = np.asarray(t["leaf_value"], dtype=np.float64)
+        feats, coeffs = [], []
+        for _ in range(lv.shape[0]):
+            m = int(rng.integers(0, max_terms + 1))
+            feats.append(rng.choice(n_features, size=m, replace=False).astype(np.int64))
+            c = rng.normal(0.0, 0.05, size=m)
+            c[rng.random(m) < 0.1] = 0.0      # exact zeros: 0.0 * inf must make a NaN score
+            coeffs.append(c)
+        t.update(leaf_const=lv + rng.normal(0.0, 0.01, size=lv.shape[0]),
+                 leaf_features=feats, leaf_coeff=coeffs)
+    return trees
+
+
+def strip_linear_leaves(trees: List[dict]) -> List[dict]:
+    """Copies of ``trees`` without the linear keys: the same splits with
+    constant leaves."""
+    keys = ("leaf_const", "leaf_features", "leaf_coeff")
+    return [{k: v for k, v in t.items() if k not in keys} for t in trees]
 
 
 def synthetic_leafwise_trees(n_trees: int, num_leaves: int, n_features: int, seed: int,
