@@ -1,0 +1,789 @@
+// treeinfer_shap.h -- TreeSHAP contributions (TI_OUTPUT_CONTRIB): the device
+// kernels, the host path tables (ShapBuilder) with their lazy build and upload
+// (ensure_shap, ensure_shap_table), and launch_contrib.  Included by
+// treeinfer.hip alone.
+#pragma once
+
+#include "treeinfer_forest.h"
+
+
+// One row per lane (64-row blocks).  Per path: the one fractions of the
+// row, then the path weights extended from scratch (ExtendPath) and, per
+// element, the unwound sum (UnwoundPathSum) times (one - zero) times the
+// leaf value, added to the element's feature.  Path weights and one
+// fractions live in LDS as [index][lane].  acc is float64 [rows, K*(F+1)];
+// the last pass divides by average_divisor, writes the bias and converts to
+// ACC.
+template <typename XT, typename ACC>
+__global__ void __launch_bounds__(64) contrib_kernel(
+    const XT* __restrict__ X, int64_t rows, int64_t stride, int32_t cols, int32_t zero_map_on,
+    const ShapPath* __restrict__ paths, int64_t n_paths, const ShapElem* __restrict__ elems,
+    const double* __restrict__ leafv, int32_t LW, int32_t K, int32_t F, int32_t maxl,
+    const double* __restrict__ bias, double divisor, double* __restrict__ acc,
+    ACC* __restrict__ out) {
+  extern __shared__ double shap_lds[];
+  const int lane = threadIdx.x;
+  const int64_t row = (int64_t)blockIdx.x * 64 + lane;
+  const bool live = row < rows;
+  double* w = shap_lds;                         // [maxl + 1][64]
+  double* ob = shap_lds + (size_t)(maxl + 1) * 64;   // [maxl][64]
+  const XT* xr = X + (live ? row : rows - 1) * stride;
+  const int W = K * (F + 1);
+  double* ph = acc + (live ? row : 0) * W;
+  for (int64_t p = 0; p < n_paths; ++p) {
+    const ShapPath P = paths[p];
+    const int n = P.n;
+    for (int i = 0; i < n; ++i) {
+      const ShapElem e = elems[P.first + i];
+      double x = e.feature < cols ? (double)xr[e.feature] : __builtin_nan("");
+      if (zero_map_on && __builtin_fabs(x) <= (double)1e-35f) x = 0.0;
+      bool follow;
+      if (x != x) follow = (e.flags & kShapNanOk) != 0;
+      else if (x == 0.0) follow = (e.flags & kShapZeroOk) != 0;
+      else follow = !(e.flags & kShapEmpty) && e.lo < x && x <= e.hi;
+      ob[i * 64 + lane] = follow ? 1.0 : 0.0;
+    }
+    w[lane] = 1.0;
+    for (int d = 1; d <= n; ++d) {
+      const double zf = elems[P.first + d - 1].zf;
+      const double of = ob[(d - 1) * 64 + lane];
+      w[d * 64 + lane] = 0.0;
+      for (int i = d - 1; i >= 0; --i) {
+        w[(i + 1) * 64 + lane] += of * w[i * 64 + lane] * (i + 1) / (double)(d + 1);
+        w[i * 64 + lane] = zf * w[i * 64 + lane] * (d - i) / (double)(d + 1);
+      }
+    }
+    for (int e_i = 1; e_i <= n; ++e_i) {
+      const ShapElem e = elems[P.first + e_i - 1];
+      const double of = ob[(e_i - 1) * 64 + lane];
+      const double zf = e.zf;
+      double next = w[n * 64 + lane];
+      double total = 0.0;
+      for (int i = n - 1; i >= 0; --i) {
+        if (of != 0.0) {
+          const double tmp = next * (n + 1) / ((i + 1) * of);
+          total += tmp;
+          next = w[i * 64 + lane] - tmp * zf * (n - i) / (double)(n + 1);
+        } else {
+          total += (w[i * 64 + lane] / zf) / ((n - i) / (double)(n + 1));
+        }
+      }
+      const double scale = total * (of - zf);
+      if (live) {
+        if (LW == 1) {
+          ph[P.group * (F + 1) + e.feature] += scale * leafv[P.leaf];
+        } else {
+          for (int k = 0; k < LW; ++k) ph[k * (F + 1) + e.feature] += scale * leafv[P.leaf * LW + k];
+        }
+      }
+    }
+  }
+  if (!live) return;
+  ACC* o = out + row * W;
+  for (int g = 0; g < K; ++g) {
+    for (int f = 0; f < F; ++f) o[g * (F + 1) + f] = (ACC)(ph[g * (F + 1) + f] / divisor);
+    o[g * (F + 1) + F] = (ACC)bias[g];
+  }
+}
+
+// 1/k for k = 0..64 (entry 0 unused), exactly rounded at compile time.
+template <int... I>
+struct ShapInvTable {
+  double v[sizeof...(I)];
+};
+template <int... I>
+constexpr ShapInvTable<I...> make_inv(std::integer_sequence<int, I...>) {
+  return {{(I == 0 ? 0.0 : 1.0 / I)...}};
+}
+__constant__ ShapInvTable kShapInv = make_inv(std::make_integer_sequence<int, 65>{});
+
+// The contrib kernel with the path arithmetic in registers.  Everything about
+// a path (its length, elements, zero fractions, leaf) is the same for all 64
+// lanes, so it comes through scalar loads; a lane only owns its row's one
+// fractions (a bitmask: they are 0 or 1) and its path weights w[0..n], which
+// stay in VGPRs because every loop that indexes them is unrolled over MAXN.
+// The divisions of contrib_kernel become products with compile-time ratios
+// or the 1/k table.  The row's contributions accumulate in LDS [W][64]
+// (W = K * (F + 1) <= kShapLdsW), so no global read-modify-write.
+constexpr int kShapLdsW = 128;
+constexpr int kShapTabStride = 8;   // coefficients per one-pattern in the table (paths of <= 8 elements)
+constexpr int64_t kShapWaveTarget = 65536;        // 64-row waves per contrib launch (sweep: profiles/r1_shap_sweep.log)
+constexpr int64_t kShapMinPathsPerSlice = 256;
+constexpr int64_t kShapMaxSlices = 64;
+constexpr uint64_t kShapPartBytesMax = 2ull << 30;
+// TAB: the per-element coefficients UnwoundPathSum x (one - zero) of every
+// path and every pattern of one fractions were computed once per forest
+// (shap_table_kernel, the same expressions in the same MT arithmetic), so a
+// path costs its n element tests, n coefficient loads at [path][om] and the
+// n accumulations, instead of the O(n^2) extend and unwind: the same floats.
+template <typename XT, typename ACC, typename MT, int MAXN, bool TAB = false>
+__global__ void __launch_bounds__(64) contrib_reg_kernel(
+    const XT* __restrict__ X, int64_t rows, int64_t stride, int32_t cols, int32_t zero_map_on,
+    const ShapPath* __restrict__ paths, int64_t n_paths, const ShapElem* __restrict__ elems,
+    const double* __restrict__ leafv, int32_t LW, int32_t K, int32_t F, int32_t maxl,
+    const double* __restrict__ bias, double divisor, double* __restrict__ part,
+    int64_t paths_per_slice, ACC* __restrict__ out, const MT* __restrict__ tab,
+    const int64_t* __restrict__ tab_off) {
+  (void)maxl;
+  extern __shared__ double shap_lds[];
+  const int lane = threadIdx.x;
+  const int64_t row = (int64_t)blockIdx.x * 64 + lane;
+  const bool live = row < rows;
+  const XT* xr = X + (live ? row : rows - 1) * stride;
+  const int W = K * (F + 1);
+  MT* phi = reinterpret_cast<MT*>(shap_lds) + lane;   // phi[j * 64]
+  for (int j = 0; j < W; ++j) phi[j * 64] = MT(0);
+  const int64_t p_begin = (int64_t)blockIdx.y * paths_per_slice;
+  const int64_t p_end = p_begin + paths_per_slice < n_paths ? p_begin + paths_per_slice : n_paths;
+  for (int64_t p = p_begin; p < p_end; ++p) {
+    const ShapPath P = paths[p];
+    const int n = P.n;
+    const ShapElem* pe = elems + P.first;
+    uint32_t om = 0u;                             // one fractions, bit i = element i
+    for (int i = 0; i < n; ++i) {
+      const ShapElem e = pe[i];
+      double x = e.feature < cols ? (double)xr[e.feature] : __builtin_nan("");
+      if (zero_map_on && __builtin_fabs(x) <= (double)1e-35f) x = 0.0;
+      bool follow;
+      if (x != x) follow = (e.flags & kShapNanOk) != 0;
+      else if (x == 0.0) follow = (e.flags & kShapZeroOk) != 0;
+      else follow = !(e.flags & kShapEmpty) && e.lo < x && x <= e.hi;
+      om |= (follow ? 1u : 0u) << i;
+    }
+    if constexpr (TAB) {
+      // the pattern's coefficients: kShapTabStride values, 32- or 64-byte
+      // aligned, read with whole-vector loads (a lane touches one line)
+      typedef MT v4_t __attribute__((ext_vector_type(4)));
+      const v4_t* c4 = reinterpret_cast<const v4_t*>(tab + tab_off[p] + (int64_t)om * kShapTabStride);
+      MT c[kShapTabStride];
+#pragma unroll
+      for (int j = 0; j < kShapTabStride / 4; ++j) {
+        const v4_t v = c4[j];
+        c[4 * j] = v.x;
+        c[4 * j + 1] = v.y;
+        c[4 * j + 2] = v.z;
+        c[4 * j + 3] = v.w;
+      }
+      const double* lv = leafv + P.leaf * LW;
+      if (LW == 1) {
+        const MT l0 = static_cast<MT>(lv[0]);
+#pragma unroll
+        for (int e_i = 0; e_i < kShapTabStride; ++e_i)
+          if (e_i < n) phi[(P.group * (F + 1) + pe[e_i].feature) * 64] += c[e_i] * l0;
+      } else {
+#pragma unroll
+        for (int e_i = 0; e_i < kShapTabStride; ++e_i)
+          if (e_i < n)
+            for (int k = 0; k < LW; ++k)
+              phi[(k * (F + 1) + pe[e_i].feature) * 64] += c[e_i] * static_cast<MT>(lv[k]);
+      }
+      continue;
+    }
+    // ExtendPath from scratch
+    MT w[MAXN + 1];
+    w[0] = MT(1);
+#pragma unroll
+    for (int d = 1; d <= MAXN; ++d) {
+      if (d <= n) {
+        const MT of = ((om >> (d - 1)) & 1u) ? MT(1) : MT(0);
+        const MT zf = static_cast<MT>(pe[d - 1].zf);
+        w[d] = MT(0);
+#pragma unroll
+        for (int i = d - 1; i >= 0; --i) {
+          w[i + 1] += of * w[i] * static_cast<MT>((double)(i + 1) / (double)(d + 1));
+          w[i] = zf * w[i] * static_cast<MT>((double)(d - i) / (double)(d + 1));
+        }
+      }
+    }
+    const MT rn1 = static_cast<MT>(n + 1);
+    const MT in1 = static_cast<MT>(kShapInv.v[n + 1]);
+    MT wn = MT(0);                              // w[n]
+#pragma unroll
+    for (int i = 0; i <= MAXN; ++i)
+      if (i == n) wn = w[i];
+    const double* lv = leafv + P.leaf * LW;
+    // UnwoundPathSum per element, times (one - zero) times the leaf value
+    if constexpr (std::is_same<MT, float>::value) {
+      // Two elements at once in packed float32 (v_pk_mul/add_f32), both
+      // branches of the unwind evaluated and selected per lane: the branch
+      // on `one` diverges within a wave anyway.  Same per-element expression
+      // order as the scalar loop below, so the same float results.
+      typedef float f2 __attribute__((ext_vector_type(2)));
+      for (int e_i = 0; e_i < n; e_i += 2) {
+        const bool pair = e_i + 1 < n;
+        const ShapElem ea = pe[e_i];
+        const ShapElem eb = pe[pair ? e_i + 1 : e_i];
+        const bool one_a = ((om >> e_i) & 1u) != 0u;
+        const bool one_b = ((om >> (pair ? e_i + 1 : e_i)) & 1u) != 0u;
+        const f2 zf = {static_cast<float>(ea.zf), static_cast<float>(eb.zf)};
+        const f2 izf = f2{1.0f, 1.0f} / zf;
+        f2 next = {wn, wn};
+        f2 tot1 = {0.0f, 0.0f}, tot0 = {0.0f, 0.0f};
+#pragma unroll
+        for (int i = MAXN - 1; i >= 0; --i) {
+          if (i < n) {
+            const f2 tmp = next * (rn1 * static_cast<float>(1.0 / (double)(i + 1)));
+            tot1 += tmp;
+            next = w[i] - tmp * zf * (static_cast<float>(n - i) * in1);
+            tot0 += w[i] * izf * (rn1 * static_cast<float>(kShapInv.v[n - i]));
+          }
+        }
+        const float sa = (one_a ? tot1.x : tot0.x) * ((one_a ? 1.0f : 0.0f) - zf.x);
+        const float sb = (one_b ? tot1.y : tot0.y) * ((one_b ? 1.0f : 0.0f) - zf.y);
+        if (LW == 1) {
+          const float l0 = static_cast<float>(lv[0]);
+          phi[(P.group * (F + 1) + ea.feature) * 64] += sa * l0;
+          if (pair) phi[(P.group * (F + 1) + eb.feature) * 64] += sb * l0;
+        } else {
+          for (int k = 0; k < LW; ++k) {
+            const float lk = static_cast<float>(lv[k]);
+            phi[(k * (F + 1) + ea.feature) * 64] += sa * lk;
+            if (pair) phi[(k * (F + 1) + eb.feature) * 64] += sb * lk;
+          }
+        }
+      }
+      continue;
+    }
+    for (int e_i = 0; e_i < n; ++e_i) {
+      const ShapElem e = pe[e_i];
+      const bool one = ((om >> e_i) & 1u) != 0u;
+      const MT zf = static_cast<MT>(e.zf);
+      MT total = MT(0);
+      if (one) {
+        MT next = wn;
+#pragma unroll
+        for (int i = MAXN - 1; i >= 0; --i) {
+          if (i < n) {
+            const MT tmp = next * (rn1 * static_cast<MT>(1.0 / (double)(i + 1)));
+            total += tmp;
+            next = w[i] - tmp * zf * (static_cast<MT>(n - i) * in1);
+          }
+        }
+      } else {
+        const MT izf = MT(1) / zf;
+#pragma unroll
+        for (int i = MAXN - 1; i >= 0; --i) {
+          if (i < n) total += w[i] * izf * (rn1 * static_cast<MT>(kShapInv.v[n - i]));
+        }
+      }
+      const MT scale = total * ((one ? MT(1) : MT(0)) - zf);
+      if (LW == 1) {
+        phi[(P.group * (F + 1) + e.feature) * 64] += scale * static_cast<MT>(lv[0]);
+      } else {
+        for (int k = 0; k < LW; ++k)
+          phi[(k * (F + 1) + e.feature) * 64] += scale * static_cast<MT>(lv[k]);
+      }
+    }
+  }
+  if (!live) return;
+  if (part) {
+    // path slice blockIdx.y: raw partial sums, [slice][W][rows] (coalesced)
+    double* pp = part + (int64_t)blockIdx.y * W * rows + row;
+    for (int j = 0; j < W; ++j) pp[(int64_t)j * rows] = static_cast<double>(phi[j * 64]);
+    return;
+  }
+  ACC* o = out + row * W;
+  for (int g = 0; g < K; ++g) {
+    for (int f = 0; f < F; ++f)
+      o[g * (F + 1) + f] = (ACC)(static_cast<double>(phi[(g * (F + 1) + f) * 64]) / divisor);
+    o[g * (F + 1) + F] = (ACC)bias[g];
+  }
+}
+
+// The coefficient table of contrib_reg_kernel<TAB>: one workgroup per path,
+// a lane per pattern om of one fractions (bit i = element i followed): the
+// path weights extended from scratch and, per element, UnwoundPathSum x
+// (one - zero) -- the expressions of contrib_reg_kernel in the same order
+// and type, so the table holds the floats the kernel would compute.
+template <typename MT, int MAXN>
+__global__ void __launch_bounds__(256) shap_table_kernel(const ShapPath* __restrict__ paths,
+                                                         const ShapElem* __restrict__ elems,
+                                                         const int64_t* __restrict__ tab_off,
+                                                         MT* __restrict__ tab) {
+  const ShapPath P = paths[blockIdx.x];
+  const int n = P.n;
+  const ShapElem* pe = elems + P.first;
+  MT* out = tab + tab_off[blockIdx.x];
+  for (uint32_t om = threadIdx.x; om < (1u << n); om += blockDim.x) {
+    MT w[MAXN + 1];
+    w[0] = MT(1);
+#pragma unroll
+    for (int d = 1; d <= MAXN; ++d) {
+      if (d <= n) {
+        const MT of = ((om >> (d - 1)) & 1u) ? MT(1) : MT(0);
+        const MT zf = static_cast<MT>(pe[d - 1].zf);
+        w[d] = MT(0);
+#pragma unroll
+        for (int i = d - 1; i >= 0; --i) {
+          w[i + 1] += of * w[i] * static_cast<MT>((double)(i + 1) / (double)(d + 1));
+          w[i] = zf * w[i] * static_cast<MT>((double)(d - i) / (double)(d + 1));
+        }
+      }
+    }
+    const MT rn1 = static_cast<MT>(n + 1);
+    const MT in1 = static_cast<MT>(kShapInv.v[n + 1]);
+    MT wn = MT(0);
+#pragma unroll
+    for (int i = 0; i <= MAXN; ++i)
+      if (i == n) wn = w[i];
+    for (int e_i = 0; e_i < n; ++e_i) {
+      const bool one = ((om >> e_i) & 1u) != 0u;
+      const MT zf = static_cast<MT>(pe[e_i].zf);
+      MT total;
+      if constexpr (std::is_same<MT, float>::value) {
+        // contrib_reg_kernel's packed float path: both sums, then the select
+        const float izf = 1.0f / zf;
+        float next = wn, tot1 = 0.0f, tot0 = 0.0f;
+#pragma unroll
+        for (int i = MAXN - 1; i >= 0; --i) {
+          if (i < n) {
+            const float tmp = next * (rn1 * static_cast<float>(1.0 / (double)(i + 1)));
+            tot1 += tmp;
+            next = w[i] - tmp * zf * (static_cast<float>(n - i) * in1);
+            tot0 += w[i] * izf * (rn1 * static_cast<float>(kShapInv.v[n - i]));
+          }
+        }
+        total = one ? tot1 : tot0;
+      } else {
+        total = MT(0);
+        if (one) {
+          MT next = wn;
+#pragma unroll
+          for (int i = MAXN - 1; i >= 0; --i) {
+            if (i < n) {
+              const MT tmp = next * (rn1 * static_cast<MT>(1.0 / (double)(i + 1)));
+              total += tmp;
+              next = w[i] - tmp * zf * (static_cast<MT>(n - i) * in1);
+            }
+          }
+        } else {
+          const MT izf = MT(1) / zf;
+#pragma unroll
+          for (int i = MAXN - 1; i >= 0; --i) {
+            if (i < n) total += w[i] * izf * (rn1 * static_cast<MT>(kShapInv.v[n - i]));
+          }
+        }
+      }
+      out[(int64_t)om * kShapTabStride + e_i] = total * ((one ? MT(1) : MT(0)) - zf);
+    }
+  }
+}
+
+// Sum of the path slices' partials in slice order, / divisor, bias column.
+template <typename ACC>
+__global__ void __launch_bounds__(256) contrib_slices_kernel(
+    const double* __restrict__ part, int32_t slices, int64_t rows, int32_t K, int32_t F,
+    const double* __restrict__ bias, double divisor, ACC* __restrict__ out) {
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= rows) return;
+  const int W = K * (F + 1);
+  ACC* o = out + row * W;
+  for (int g = 0; g < K; ++g) {
+    for (int f = 0; f < F; ++f) {
+      const int j = g * (F + 1) + f;
+      double t = 0.0;
+      for (int sl = 0; sl < slices; ++sl) t += part[((int64_t)sl * W + j) * rows + row];
+      o[j] = (ACC)(t / divisor);
+    }
+    o[g * (F + 1) + F] = (ACC)bias[g];
+  }
+}
+
+namespace {
+
+int ensure_lds_attr(int device, KernelFn fn);   // treeinfer.hip
+
+// the TreeSHAP buffers of one replica (device current), after a failed upload
+// or with the replica; the caller restores `bytes`
+void free_shap(DeviceForest& d) {
+  d.shap_mem.release();
+  static_cast<ShapPtrs&>(d) = ShapPtrs();
+  d.shap_tab_state = 0;
+}
+
+// TreeSHAP path tables + bias (see ShapPath).  Forests without covers or
+// with categorical splits get none (TI_OUTPUT_CONTRIB is then unsupported).
+struct ShapBuilder {
+  const ti_forest_desc* d;
+  ti_forest* f;
+  int64_t b = 0;
+  int group = 0;
+  std::vector<ShapElem> cur;
+
+  void dfs(int32_t v) {
+    const int64_t g = b + v;
+    const int LW = d->leaf_width;
+    if (d->feature[g] < 0) {
+      ShapPath p;
+      p.group = group;
+      p.n = static_cast<int32_t>(cur.size());
+      p.first = static_cast<int64_t>(f->h_elems.size());
+      p.leaf = static_cast<int64_t>(f->h_path_leaf.size()) / LW;
+      f->h_elems.insert(f->h_elems.end(), cur.begin(), cur.end());
+      for (int k = 0; k < LW; ++k) f->h_path_leaf.push_back(d->leaf_value[g * LW + k]);
+      f->h_paths.push_back(p);
+      f->shap_maxl = std::max(f->shap_maxl, p.n);
+      return;
+    }
+    const int32_t fe = d->feature[g];
+    const double t = d->threshold[g];
+    const bool nan_left = (d->flags[g] & TI_NODE_NAN_LEFT) != 0;
+    const bool zero_left = (d->flags[g] & TI_NODE_ZERO_FLIP) ? !(0 <= t) : (0 <= t);
+    for (int side = 0; side < 2; ++side) {
+      const bool left = side == 0;
+      const int32_t child = left ? d->left[g] : d->right[g];
+      const std::vector<ShapElem> saved = cur;
+      ShapElem e{fe, kShapNanOk | kShapZeroOk, -INFINITY, INFINITY, 1.0};
+      for (size_t i = 0; i < cur.size(); ++i)
+        if (cur[i].feature == fe) {   // unwind the earlier split on fe, re-extend at the end
+          e = cur[i];
+          cur.erase(cur.begin() + static_cast<std::ptrdiff_t>(i));
+          break;
+        }
+      e.zf = (d->cover[b + child] / d->cover[g]) * e.zf;
+      if (left) {
+        if (std::isnan(t)) e.flags |= kShapEmpty;
+        else e.hi = std::min(e.hi, t);
+      } else if (!std::isnan(t)) {
+        e.lo = std::max(e.lo, t);
+      }
+      if (nan_left != left) e.flags &= ~kShapNanOk;
+      if (zero_left != left) e.flags &= ~kShapZeroOk;
+      cur.push_back(e);
+      dfs(child);
+      cur = saved;
+    }
+  }
+
+  std::vector<double> mean(int32_t v) {   // FillNodeMeanValues, per leaf-vector entry
+    const int64_t g = b + v;
+    const int LW = d->leaf_width;
+    std::vector<double> r(LW);
+    if (d->feature[g] < 0) {
+      for (int k = 0; k < LW; ++k) r[k] = d->leaf_value[g * LW + k];
+      return r;
+    }
+    const int32_t l = d->left[g], rr = d->right[g];
+    const std::vector<double> ml = mean(l), mr = mean(rr);
+    for (int k = 0; k < LW; ++k)
+      r[k] = (ml[k] * d->cover[b + l] + mr[k] * d->cover[b + rr]) / d->cover[g];
+    return r;
+  }
+};
+
+// At create: whether contributions are possible (covers, no categorical
+// splits), and the host copy build_shap will read on first use.
+void keep_shap_source(const ti_forest_desc* d, ti_forest* f) {
+  if (!d->cover) return;
+  for (int64_t g = 0; g < d->n_nodes; ++g)
+    if (d->feature[g] >= 0 && (d->flags[g] & TI_NODE_CATEGORICAL)) return;
+  auto src = std::make_unique<ti_forest::ShapSource>();
+  const int64_t N = d->n_nodes, T = d->n_trees;
+  src->tree_offset.assign(d->tree_offset, d->tree_offset + T + 1);
+  if (d->tree_group) src->tree_group.assign(d->tree_group, d->tree_group + T);
+  src->feature.assign(d->feature, d->feature + N);
+  src->left.assign(d->left, d->left + N);
+  src->right.assign(d->right, d->right + N);
+  src->threshold.assign(d->threshold, d->threshold + N);
+  src->leaf_value.assign(d->leaf_value, d->leaf_value + N * d->leaf_width);
+  src->base_margin.assign(d->base_margin, d->base_margin + d->n_groups);
+  src->cover.assign(d->cover, d->cover + N);
+  src->flags.assign(d->flags, d->flags + N);
+  src->desc = *d;
+  src->desc.tree_offset = src->tree_offset.data();
+  src->desc.tree_group = src->tree_group.empty() ? nullptr : src->tree_group.data();
+  src->desc.feature = src->feature.data();
+  src->desc.left = src->left.data();
+  src->desc.right = src->right.data();
+  src->desc.threshold = src->threshold.data();
+  src->desc.leaf_value = src->leaf_value.data();
+  src->desc.base_margin = src->base_margin.data();
+  src->desc.cover = src->cover.data();
+  src->desc.flags = src->flags.data();
+  src->desc.leaf_id = nullptr;
+  src->desc.cat_bits = nullptr;
+  src->desc.cat_offset = nullptr;
+  src->desc.cat_nwords = nullptr;
+  f->shap_src = std::move(src);
+  f->has_shap = 1;
+}
+
+void build_shap(const ti_forest_desc* d, ti_forest* f) {
+  const int K = d->n_groups;
+  std::vector<double> bias(K);
+  for (int k = 0; k < K; ++k) bias[k] = d->base_margin[k] * d->average_divisor;
+  ShapBuilder sb{d, f};
+  for (int t = 0; t < d->n_trees; ++t) {
+    sb.b = d->tree_offset[t];
+    sb.group = d->leaf_width == 1 ? d->tree_group[t] : 0;
+    sb.cur.clear();
+    sb.dfs(0);
+    const std::vector<double> m = sb.mean(0);
+    if (d->leaf_width == 1) bias[sb.group] += m[0];
+    else for (int k = 0; k < K; ++k) bias[k] += m[k];
+  }
+  f->h_shap_bias.resize(K);
+  for (int k = 0; k < K; ++k) f->h_shap_bias[k] = bias[k] / d->average_divisor;
+  f->shap_npaths = static_cast<int64_t>(f->h_paths.size());
+}
+
+// TI_OUTPUT_CONTRIB on one (unchunked) forest.  contrib_reg_kernel when the
+// row's accumulators fit LDS (K * (F + 1) <= kShapLdsW) and paths have <= 32
+// unique features: path slices over blockIdx.y, partials summed in slice
+// order by contrib_slices_kernel.  Otherwise contrib_kernel, whose float32
+// forests accumulate in a float64 scratch.
+// First contributions call: build the path tables on the host and upload them
+// to every device replica (under the forest's lock; later calls see
+// shap_ready and skip it).
+int ensure_shap(ti_forest* f) {
+  if (f->shap_ready.load(std::memory_order_acquire)) return TI_OK;
+  std::lock_guard<std::mutex> lk(f->shap_mu);
+  if (f->shap_ready.load(std::memory_order_relaxed)) return TI_OK;
+  if (f->h_paths.empty()) build_shap(&f->shap_src->desc, f);
+  // the coefficient table's shape (contrib_reg_kernel TAB): paths of <= 8
+  // unique features, 2^n x 8 coefficients each (padded), in the path
+  // arithmetic's type.  The table itself is built per replica, later, by
+  // ensure_shap_table.
+  {
+    const int mt = (f->accum != TI_F64 && !env_int("TI_SHAP_F64", 0)) ? 4 : 8;
+    const int64_t W = static_cast<int64_t>(f->K) * (f->F + 1);
+    f->h_tab_off.assign(f->h_paths.size(), 0);
+    int64_t len = 0;
+    bool ok = W <= kShapLdsW && f->shap_maxl <= kShapTabStride && !f->h_paths.empty();
+    for (size_t i = 0; ok && i < f->h_paths.size(); ++i) {
+      f->h_tab_off[i] = len;
+      len += (int64_t(1) << f->h_paths[i].n) * kShapTabStride;
+    }
+    f->shap_tab_mt = ok ? mt : 0;
+    f->shap_tab_len = ok ? len : 0;
+    if (!ok) f->h_tab_off.clear();
+  }
+  int dev0 = 0;
+  TI_HIP(hipGetDevice(&dev0));
+  int rc = TI_OK;
+  // each replica's byte count before the uploads: a failure restores it, so
+  // ti_forest_info's device_bytes does not keep the freed tables
+  std::vector<int64_t> bytes0;
+  for (auto& dp : f->devs) bytes0.push_back(dp->bytes);
+  for (auto& dp : f->devs) {
+    DeviceForest& d = *dp;
+    if ((rc = fail_hip(hipSetDevice(d.device), "hipSetDevice"))) break;
+    if ((rc = upload(&d.shap_mem, &d.shap_paths, f->h_paths, &d.bytes)) ||
+        (rc = upload(&d.shap_mem, &d.shap_elems, f->h_elems, &d.bytes)) ||
+        (rc = upload(&d.shap_mem, &d.shap_leaf, f->h_path_leaf, &d.bytes)) ||
+        (rc = upload(&d.shap_mem, &d.shap_bias, f->h_shap_bias, &d.bytes)))
+      break;
+  }
+  if (rc) {
+    // nothing half-built survives: every replica's path tables are freed (the
+    // host tables stay, so the next call retries from them)
+    const std::string err = g_last_error;
+    for (size_t i = 0; i < f->devs.size(); ++i) {
+      (void)hipSetDevice(f->devs[i]->device);
+      free_shap(*f->devs[i]);
+      f->devs[i]->bytes = bytes0[i];
+    }
+    (void)hipGetLastError();
+    (void)hipSetDevice(dev0);
+    return fail(rc, err);
+  }
+  TI_HIP(hipSetDevice(dev0));
+  f->h_paths.clear(); f->h_paths.shrink_to_fit();
+  f->h_elems.clear(); f->h_elems.shrink_to_fit();
+  f->h_path_leaf.clear(); f->h_path_leaf.shrink_to_fit();
+  f->shap_src.reset();
+  f->shap_ready.store(true, std::memory_order_release);
+  return TI_OK;
+}
+
+// The coefficient table of one replica (device d.device current), built on
+// the first contributions batch that would use it.  It is an optimisation
+// only: any failure (over the size cap, allocation, launch) frees what was
+// allocated, clears the HIP error and marks the replica, whose contributions
+// then take the extend / unwind kernel -- never an error for the caller.  The
+// build runs on a private stream and waits for that stream alone.
+void ensure_shap_table(ti_forest* f, DeviceForest& d) {
+  std::lock_guard<std::mutex> lk(f->shap_mu);
+  if (d.shap_tab_state != 0) return;
+  d.shap_tab_state = -1;
+  const size_t bytes = static_cast<size_t>(f->shap_tab_len) * f->shap_tab_mt;
+  if (!f->shap_tab_mt || f->shap_tab_mb <= 0 ||
+      bytes > (static_cast<size_t>(f->shap_tab_mb) << 20))
+    return;
+  const auto t0 = std::chrono::steady_clock::now();
+  hipStream_t s = nullptr;
+  bool ok = hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess;
+  int64_t up = 0;
+  DeviceAllocs mem;   // the table's two buffers: joined to shap_mem once built
+  ok = ok && !env_int("TI_SHAP_TABLE_FAULT", 0) &&   // fault injection (tests)
+       upload(&mem, &d.shap_tab_off, f->h_tab_off, &up) == TI_OK &&
+       hipMalloc(&d.shap_tab, std::max<size_t>(bytes, 16)) == hipSuccess;
+  if (ok) mem.ptrs.push_back(d.shap_tab);
+  if (ok) {
+    const unsigned np = static_cast<unsigned>(f->h_tab_off.size());
+    if (f->shap_tab_mt == 4)
+      hipLaunchKernelGGL((shap_table_kernel<float, 16>), dim3(np), dim3(256), 0, s,
+                         d.shap_paths, d.shap_elems, d.shap_tab_off, static_cast<float*>(d.shap_tab));
+    else
+      hipLaunchKernelGGL((shap_table_kernel<double, 16>), dim3(np), dim3(256), 0, s,
+                         d.shap_paths, d.shap_elems, d.shap_tab_off, static_cast<double*>(d.shap_tab));
+    ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+  }
+  if (s) (void)hipStreamDestroy(s);
+  if (!ok) {
+    mem.release();
+    d.shap_tab = nullptr;
+    d.shap_tab_off = nullptr;
+    (void)hipGetLastError();
+    return;
+  }
+  d.shap_mem.ptrs.insert(d.shap_mem.ptrs.end(), mem.ptrs.begin(), mem.ptrs.end());
+  d.bytes += up + static_cast<int64_t>(bytes);
+  d.shap_tab_state = 1;
+  f->shap_tab_build_ms =
+      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+int launch_contrib(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows,
+                   int32_t cols, int64_t stride, void* out, hipStream_t stream) {
+  if (!f->has_shap)
+    return fail(TI_ERR_UNSUPPORTED,
+                "contributions need node covers (ti_forest_desc.cover) and no categorical splits");
+  {
+    const int rc = ensure_shap(f);
+    if (rc) return rc;
+  }
+  const int64_t W = static_cast<int64_t>(f->K) * (f->F + 1);
+  const int64_t n_paths = static_cast<int64_t>(d.shap_paths ? 1 : 0) * f->shap_npaths;
+  const int force_generic = env_int("TI_SHAP_GENERIC", 0);
+  if (W <= kShapLdsW && f->shap_maxl <= 32 && !force_generic) {
+    // registers + LDS accumulators: no scratch accumulator, no memset
+    const int maxn = f->shap_maxl <= 8 ? 8 : f->shap_maxl <= 16 ? 16 : 32;
+    const int force_f64 = env_int("TI_SHAP_F64", 0);
+    const bool f32_math = f->accum != TI_F64 && !force_f64;
+    const size_t lds_w = static_cast<size_t>(W) * 64 * (f32_math ? 4 : 8);
+    const unsigned grid_r = static_cast<unsigned>((rows + 63) / 64);
+    if (rows == 0) return TI_OK;
+    // Path slices: one 64-row wave walks n_paths / slices paths, so a small
+    // batch still fills the 256 CUs (>= kShapWaveTarget waves); partials
+    // [slices][W][rows] are summed in slice order by contrib_slices_kernel.
+    const int force_slices = env_int("TI_SHAP_SLICES", 0);
+    int64_t slices = force_slices > 0 ? force_slices
+                                      : (kShapWaveTarget + grid_r - 1) / static_cast<int64_t>(grid_r);
+    slices = std::min<int64_t>(slices, std::max<int64_t>(1, n_paths / kShapMinPathsPerSlice));
+    slices = std::min<int64_t>(slices, kShapMaxSlices);
+    while (slices > 1 && static_cast<uint64_t>(slices) * W * rows * 8 > kShapPartBytesMax) --slices;
+    slices = std::max<int64_t>(slices, 1);
+    const int64_t pps = (n_paths + slices - 1) / slices;
+    // the coefficient table pays off for small batches (C2 model: 4,096 rows
+    // 4.1e5 vs 2.7e5 rows/s); at 100k rows its gathers (a 64-row wave reads
+    // most of each path's 2^n x 32 B block) make it slower than the extend /
+    // unwind arithmetic (2.2e5 vs 2.9e5): profiles/r3_shap_table.jsonl
+    const bool want_tab = f->shap_tab_mt != 0 && rows <= f->shap_tab_rows;
+    if (want_tab && d.shap_tab_state == 0) ensure_shap_table(f, d);
+    double* part = nullptr;
+    if (slices > 1)
+      TI_HIP(hipMallocAsync(reinterpret_cast<void**>(&part),
+                            static_cast<size_t>(slices * W * rows) * 8, stream));
+#define TI_CONTRIB_REG(XT_, ACC_, MT_, N_)                                                          \
+  do {                                                                                         \
+    const bool tab_ = want_tab && d.shap_tab_state == 1 &&                                     \
+                      f->shap_tab_mt == (int)sizeof(MT_);                                      \
+    KernelFn fn_ = tab_ ? reinterpret_cast<KernelFn>(contrib_reg_kernel<XT_, ACC_, MT_, 8, true>) \
+                        : reinterpret_cast<KernelFn>(contrib_reg_kernel<XT_, ACC_, MT_, N_>);  \
+    int rc_ = ensure_lds_attr(d.device, fn_);                                                  \
+    if (rc_) return rc_;                                                                       \
+    if (tab_)                                                                                  \
+      hipLaunchKernelGGL((contrib_reg_kernel<XT_, ACC_, MT_, 8, true>), dim3(grid_r, (unsigned)slices), \
+                         dim3(64), lds_w, stream,                                              \
+                         static_cast<const XT_*>(X), rows, stride, cols, f->lgb_zero_map,      \
+                         d.shap_paths, n_paths, d.shap_elems, d.shap_leaf, f->LW, f->K, f->F,  \
+                         f->shap_maxl, d.shap_bias, f->divisor, part, pps, static_cast<ACC_*>(out), \
+                         static_cast<const MT_*>(d.shap_tab), d.shap_tab_off);                 \
+    else                                                                                       \
+      hipLaunchKernelGGL((contrib_reg_kernel<XT_, ACC_, MT_, N_>), dim3(grid_r, (unsigned)slices), dim3(64), \
+                         lds_w, stream,                                                        \
+                         static_cast<const XT_*>(X), rows, stride, cols, f->lgb_zero_map,      \
+                         d.shap_paths, n_paths, d.shap_elems, d.shap_leaf, f->LW, f->K, f->F,  \
+                         f->shap_maxl, d.shap_bias, f->divisor, part, pps, static_cast<ACC_*>(out), \
+                         static_cast<const MT_*>(nullptr), static_cast<const int64_t*>(nullptr)); \
+    if (part) {                                                                                \
+      const unsigned g2 = static_cast<unsigned>((rows + 255) / 256);                           \
+      hipLaunchKernelGGL((contrib_slices_kernel<ACC_>), dim3(g2), dim3(256), 0, stream, part,  \
+                         (int32_t)slices, rows, f->K, f->F, d.shap_bias, f->divisor,           \
+                         static_cast<ACC_*>(out));                                             \
+    }                                                                                          \
+  } while (0)
+#define TI_CONTRIB_REG_N(XT_, ACC_, MT_)                     \
+  do {                                                       \
+    if (maxn == 8) TI_CONTRIB_REG(XT_, ACC_, MT_, 8);        \
+    else if (maxn == 16) TI_CONTRIB_REG(XT_, ACC_, MT_, 16); \
+    else TI_CONTRIB_REG(XT_, ACC_, MT_, 32);                 \
+  } while (0)
+    // Path arithmetic in the forest's accumulator type: float64 for LightGBM
+    // and sklearn; float32 for XGBoost, whose TreeShap keeps its path
+    // elements and contributions in bst_float (TI_SHAP_F64=1 forces
+    // float64).  Each slice accumulates in that type in LDS (float32 halves
+    // the LDS per workgroup: 2x workgroups per CU); slices sum in float64.
+    if (xdt == TI_F32) {
+      if (f->accum == TI_F64) TI_CONTRIB_REG_N(float, double, double);
+      else if (f32_math) TI_CONTRIB_REG_N(float, float, float);
+      else TI_CONTRIB_REG_N(float, float, double);
+    } else {
+      if (f->accum == TI_F64) TI_CONTRIB_REG_N(double, double, double);
+      else if (f32_math) TI_CONTRIB_REG_N(double, float, float);
+      else TI_CONTRIB_REG_N(double, float, double);
+    }
+#undef TI_CONTRIB_REG_N
+#undef TI_CONTRIB_REG
+    TI_HIP(hipGetLastError());
+    if (part) TI_HIP(hipFreeAsync(part, stream));
+    return TI_OK;
+  }
+  double* acc = nullptr;
+  if (f->accum == TI_F64) {
+    acc = static_cast<double*>(out);
+  } else {
+    TI_HIP(hipMallocAsync(reinterpret_cast<void**>(&acc), static_cast<size_t>(rows * W) * 8, stream));
+  }
+  TI_HIP(hipMemsetAsync(acc, 0, static_cast<size_t>(rows * W) * 8, stream));
+  const size_t lds = static_cast<size_t>(2 * f->shap_maxl + 1) * 64 * 8;
+  KernelFn fn;
+  if (xdt == TI_F32)
+    fn = f->accum == TI_F64 ? reinterpret_cast<KernelFn>(contrib_kernel<float, double>)
+                            : reinterpret_cast<KernelFn>(contrib_kernel<float, float>);
+  else
+    fn = f->accum == TI_F64 ? reinterpret_cast<KernelFn>(contrib_kernel<double, double>)
+                            : reinterpret_cast<KernelFn>(contrib_kernel<double, float>);
+  int rc = ensure_lds_attr(d.device, fn);
+  if (rc) return rc;
+  const unsigned grid = static_cast<unsigned>((rows + 63) / 64);
+  if (xdt == TI_F32) {
+    if (f->accum == TI_F64)
+      hipLaunchKernelGGL((contrib_kernel<float, double>), dim3(grid), dim3(64), lds, stream,
+                         static_cast<const float*>(X), rows, stride, cols, f->lgb_zero_map,
+                         d.shap_paths, n_paths, d.shap_elems, d.shap_leaf, f->LW, f->K, f->F,
+                         f->shap_maxl, d.shap_bias, f->divisor, acc, static_cast<double*>(out));
+    else
+      hipLaunchKernelGGL((contrib_kernel<float, float>), dim3(grid), dim3(64), lds, stream,
+                         static_cast<const float*>(X), rows, stride, cols, f->lgb_zero_map,
+                         d.shap_paths, n_paths, d.shap_elems, d.shap_leaf, f->LW, f->K, f->F,
+                         f->shap_maxl, d.shap_bias, f->divisor, acc, static_cast<float*>(out));
+  } else {
+    if (f->accum == TI_F64)
+      hipLaunchKernelGGL((contrib_kernel<double, double>), dim3(grid), dim3(64), lds, stream,
+                         static_cast<const double*>(X), rows, stride, cols, f->lgb_zero_map,
+                         d.shap_paths, n_paths, d.shap_elems, d.shap_leaf, f->LW, f->K, f->F,
+                         f->shap_maxl, d.shap_bias, f->divisor, acc, static_cast<double*>(out));
+    else
+      hipLaunchKernelGGL((contrib_kernel<double, float>), dim3(grid), dim3(64), lds, stream,
+                         static_cast<const double*>(X), rows, stride, cols, f->lgb_zero_map,
+                         d.shap_paths, n_paths, d.shap_elems, d.shap_leaf, f->LW, f->K, f->F,
+                         f->shap_maxl, d.shap_bias, f->divisor, acc, static_cast<float*>(out));
+  }
+  TI_HIP(hipGetLastError());
+  if (acc != out) TI_HIP(hipFreeAsync(acc, stream));
+  return TI_OK;
+}
+
+}  // namespace
