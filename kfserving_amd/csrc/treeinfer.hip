@@ -253,7 +253,7 @@ struct LaunchPlan {
 
 // Plans the launch of forest f (device copy d) for batches of input type xdt
 // and output `kind`.  Host arithmetic only: it makes no HIP call, and reads
-// the knobs TI_BHEAP_FIX / TI_BHEAP_NG (every call) and TI_HEAP_LDS_KB /
+// the knobs TI_BHEAP_FIX / TI_BHEAP_NG / TI_BIN_XPF (every call) and TI_HEAP_LDS_KB /
 // TI_BHEAP_STAGE (once).
 int plan_launch(const ti_forest* f, const DeviceForest& d, int xdt, int kind, LaunchPlan* p) {
   const size_t xs = dtype_size(xdt);
@@ -323,6 +323,7 @@ int plan_launch(const ti_forest* f, const DeviceForest& d, int xdt, int kind, La
     S = std::min<int64_t>(S, f->T);
     a.bin_mask = bi.mask;
     a.bin_kary = bi.kary;
+    a.bin_nb = bi.bkt_nb;
     a.trees = d.bh_img[ii];
     a.tree_stride = stride_b;
     a.heap_leaf_ids = d.heap_leaf_ids;
@@ -349,6 +350,7 @@ int plan_launch(const ti_forest* f, const DeviceForest& d, int xdt, int kind, La
       key.groups = ng;
       a.stage_trees = 4 * ng;
       a.bin_chunk = 4 * ng;
+      a.bin_xpf = env_int("TI_BIN_XPF", 1) != 0;   // stage_bins' register path (NG = 1)
       a.stage_off = static_cast<int32_t>(ti::kFixStage);
       if (d.bh_fix_img != nullptr) a.trees = d.bh_fix_img;   // same walk, hot pair slots first
       p->lds = ti::kFixStage + static_cast<size_t>(4 * ng) * ti::kFixTree;

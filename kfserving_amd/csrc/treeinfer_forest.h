@@ -293,6 +293,7 @@ struct DeviceForest : ForestPtrs, ShapPtrs, ScratchBufs {
 struct BinPlan {
   int32_t L = 0;
   int32_t kary = 0;                 // > 0: tbl holds float32 5-ary tables of this height
+  int32_t bkt_nb = 0;               // > 0: tbl holds float32 bucket tables of this many buckets
   int32_t b16 = 1;
   int32_t rows = 256;
   int32_t words = 0;                // packed bin words per row
@@ -302,7 +303,8 @@ struct BinPlan {
 struct BinImage : BinPlan {
   std::vector<unsigned char> img;   // [T][stride]
   std::vector<unsigned char> fix_img;   // img with hot pair slots first (fix_permute), or empty
-  std::vector<unsigned char> tbl;   // [F][2^L] XT Eytzinger tables, or 5-ary (kary > 0)
+  std::vector<unsigned char> tbl;   // [F][2^L] XT Eytzinger tables, 5-ary (kary > 0) or
+                                    // bucket tables (bkt_nb > 0)
 };
 
 // Record explicit layout (6): 8-byte slots per input dtype (ranks differ),

@@ -114,6 +114,8 @@ struct KArgs {
   const void* bin_tbl;            // [F][2^bin_L] Eytzinger threshold tables, XT
   int32_t bin_L;                  // search depth (common to all features)
   int32_t bin_kary;               // > 0: float32 5-ary search tables of this height (rx_stage_bins)
+  int32_t bin_nb;                 // > 0: bin_tbl holds bucket tables of this many buckets (rank_search)
+  int32_t bin_xpf;                // stage_bins: load the next chunk's X before searching this one
   int32_t bin_words;              // packed bin words per row (C)
   int32_t bin_chunk;              // columns binned per pass through the temp area
   int32_t stage_off;              // LDS byte offset of the tree stage / temp area
@@ -532,21 +534,78 @@ __device__ __forceinline__ uint32_t kpow5(int h) {
   return p;
 }
 
+// The bucket of x among nb equal-width buckets from lo: trunc((x - lo) * scale)
+// clamped to [0, nb - 1], the subtract and the multiply rounded separately (no
+// FMA).  The host builds the bucket tables with this very function and the
+// device indexes them with it, so both see the same float32 operations; it is
+// monotone non-decreasing in x for scale >= 0 (each step is), which is all the
+// search needs.  NaN, +-inf and out-of-range products land in range: the float
+// clamp drops a NaN (fmaxf returns the other operand), the integer clamp
+// bounds whatever the conversion gives.
+__host__ __device__ __forceinline__ uint32_t bin_bucket(float x, float lo, float scale, int32_t nb) {
+#ifdef __HIP_DEVICE_COMPILE__
+  float t = __fmul_rn(__fsub_rn(x, lo), scale);
+#else
+  volatile float d = x - lo;   // rounded on its own whatever the host's contraction setting
+  float t = d * scale;
+#endif
+  t = fminf(fmaxf(t, 0.0f), static_cast<float>(nb - 1));
+  int32_t k = static_cast<int32_t>(t);
+  k = k < 0 ? 0 : k;
+  k = k > nb - 1 ? nb - 1 : k;
+  return static_cast<uint32_t>(k);
+}
+
 // b[q] = 1 + #{u in U_f : u < x[q]} for Q consecutive features f0 + q (the
 // last feature repeated past F; NaN gives an unspecified b, the caller codes
-// it).  Two table forms (host: eytzinger_tables / kary_tables):
+// it).  Three table forms (host: eytzinger_tables / kary_tables /
+// bucket_tables):
 //  * Eytzinger: 2^L entries per feature, node k's children 2k and 2k+1,
 //    +inf padded: L dependent 4- or 8-byte gathers;
 //  * 5-ary (float32 view, a.bin_kary = H > 0): node j holds 4 sorted keys in
 //    16 B, children 5j+1 .. 5j+5; after H levels j - (5^H - 1)/4 is the
-//    count: H dependent 16-byte gathers (C2: 6 instead of 13).
+//    count: H dependent 16-byte gathers (C2: 6 instead of 13);
+//  * bucket-first (float32 view of the binned heap, a.bin_nb = NB > 0; built
+//    where no bucket holds more than 4 thresholds, bucket_tables): per feature
+//    {lo, scale, first key}, start[NB] u16, and every feature's sorted
+//    thresholds followed by 4 +inf.  start[bin_bucket(x)] counts the
+//    thresholds of the lower buckets, all < x; those of the higher buckets
+//    are all >= x, so the rank is that count plus the keys below x among the
+//    next 4 sorted thresholds, which cover the bucket: 2 dependent gathers.
+//    Both are divergent, where the 5-ary tree's top levels sit in a few cache
+//    lines, so more loads per value do not pay (c2_hist's 2
+//    against 4 gain 2 %, C2's 1 + 3 against 6 lost 9 %).
 // Q independent chains per lane hide the L2 latency of each level.
 template <typename XT, int Q>
 __device__ __forceinline__ void rank_search(const KArgs& a, const XT (&x)[Q], int f0,
                                             uint32_t (&b)[Q]) {
   const int F = a.n_features;
   uint32_t tq[Q], k[Q];
-  if (sizeof(XT) == 4 && a.bin_kary > 0) {
+  if (sizeof(XT) == 4 && a.bin_nb > 0) {
+    const uint32_t nb = (uint32_t)a.bin_nb;
+    const uint4* fs = reinterpret_cast<const uint4*>(a.bin_tbl);
+    const uint16_t* start = reinterpret_cast<const uint16_t*>(fs + F);
+    const float* srt = reinterpret_cast<const float*>(start + (size_t)F * nb);
+    // the keys: one 16-byte load at 4-byte alignment (global memory takes
+    // unaligned addresses)
+    typedef float f4u_t __attribute__((ext_vector_type(4), aligned(4)));
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const uint32_t f = (uint32_t)(f0 + q < F ? f0 + q : F - 1);   // uniform: a scalar load
+      const uint4 p = fs[f];
+      k[q] = start[f * nb + bin_bucket((float)x[q], __uint_as_float(p.x), __uint_as_float(p.y), a.bin_nb)];
+      tq[q] = p.z + k[q];
+    }
+    f4u_t e[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) e[q] = *reinterpret_cast<const f4u_t*>(srt + tq[q]);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const float xv = (float)x[q];
+      b[q] = 1u + k[q] + (e[q].x < xv ? 1u : 0u) + (e[q].y < xv ? 1u : 0u) + (e[q].z < xv ? 1u : 0u) +
+             (e[q].w < xv ? 1u : 0u);
+    }
+  } else if (sizeof(XT) == 4 && a.bin_kary > 0) {
     typedef float f4_t __attribute__((ext_vector_type(4)));
     const f4_t* t4 = reinterpret_cast<const f4_t*>(a.bin_tbl);
     const uint32_t nn = (kpow5(a.bin_kary) - 1u) / 4u;   // nodes per feature
@@ -589,13 +648,53 @@ __device__ __forceinline__ void rank_search(const KArgs& a, const XT (&x)[Q], in
   }
 }
 
-// Bin the tile's rows into the LDS bin image (at LDS address 0).  Columns go
-// through `temp` (the tree-stage area, free at this point) bin_chunk at a
-// time: a coalesced copy into [c][R], then every lane searches its own row's
-// values (rank_search), Q features at once for Q independent load chains.
+// Rank the lane's values x[0 .. Q) of features f .. f + Q - 1 (the first n of
+// them live) and store the packed bin words of row `tid` in the bin image.
+// Returns whether a live value is a NaN.
+template <typename XT, bool B16, int Q>
+__device__ __forceinline__ bool bin_commit(const KArgs& a, const XT (&x)[Q], int f, int n, int R,
+                                           int tid) {
+  using BT = BinTraits<B16>;
+  constexpr int P = BT::P;
+  uint32_t b[Q];
+  rank_search<XT, Q>(a, x, f, b);
+  uint32_t w[Q / P];
+  bool has_nan = false;
+#pragma unroll
+  for (int j = 0; j < Q / P; ++j) w[j] = 0u;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const bool nan = x[q] != x[q];
+    has_nan |= nan && (q < n);
+    w[q / P] |= (nan ? BT::kNan : b[q]) << ((q % P) * (32 / P));
+  }
+#pragma unroll
+  for (int j = 0; j < Q / P; ++j) {
+    const int word = f / P + j;
+    if (j * P < n) {
+      __attribute__((address_space(3))) uint32_t* dst =
+          reinterpret_cast<__attribute__((address_space(3))) uint32_t*>(
+              static_cast<uintptr_t>((uint32_t)(word * R + tid) * 4u));
+      *dst = w[j];
+    }
+  }
+  return has_nan;
+}
+
+// Bin the tile's rows into the LDS bin image (at LDS address 0).  Two ways in:
+//  * registers (a.bin_xpf, the fixed walk's default: aligned rows, chunks of
+//    one 16-byte load per lane): every lane loads and searches segments of its
+//    own row, the next segment's load in flight during this one's search.
+//    Compiled in with REGS only: the fixed kernels of at most 4 output groups
+//    (42-44 VGPRs, 92-98 SGPRs, 8 waves per SIMD with it; the 16-group ones
+//    sit at 64 VGPRs, and its scalars took them to 106 SGPRs and 7 waves);
+//  * through `temp` (the tree-stage area, free at this point) bin_chunk
+//    columns at a time: a coalesced copy into [c][R], then every lane searches
+//    its own row's values (rank_search), Q features at once for Q independent
+//    load chains.
 // Returns (uniformly) whether a live row of the tile holds a NaN.  Ends in a
 // barrier.
-template <typename XT, bool B16, int Q = TI_BIN_Q>
+template <typename XT, bool B16, int Q = TI_BIN_Q, bool REGS = false>
 __device__ __forceinline__ bool stage_bins(volatile int* flag, XT* temp, const KArgs& a,
                                            int64_t row0, int R, int tid) {
   using BT = BinTraits<B16>;
@@ -609,10 +708,35 @@ __device__ __forceinline__ bool stage_bins(volatile int* flag, XT* temp, const K
   const bool vec_ok = ((reinterpret_cast<uintptr_t>(X) | (uintptr_t)(a.row_stride * sizeof(XT))) & 15) == 0;
   bool has_nan = false;
   if (tid == 0) *flag = 0;
+  constexpr int V = 16 / sizeof(XT);   // elements per 16-byte load
+  if constexpr (Q == V && REGS) {
+    // Chunks of one 16-byte load per lane (the fixed walk's 4 float columns),
+    // every one whole and aligned: lane `tid` loads a segment of its own row
+    // and searches those very values, so they stay in registers -- no pass
+    // through temp, no barrier per chunk -- and the next chunk's load is
+    // issued before this chunk's search, which hides its latency: one exposed
+    // X round trip per tile instead of one per chunk.  A lane past the batch
+    // bins the tile's first row (its NaN does not count below).
+    if (a.bin_xpf != 0 && vec_ok && a.bin_chunk == V && F % V == 0 && F <= C) {
+      typedef XT xv_t __attribute__((ext_vector_type(V)));
+      const XT* xr = X + (row0 + (tid < rows_here ? tid : 0)) * a.row_stride;
+      xv_t nx = *reinterpret_cast<const xv_t*>(xr);
+      __syncthreads();   // the flag is cleared before any lane raises it
+      for (int f0 = 0; f0 < F; f0 += V) {
+        XT x[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) x[q] = zero_map(nx[q], a.lgb_zero_map);
+        if (f0 + V < F) nx = *reinterpret_cast<const xv_t*>(xr + f0 + V);
+        has_nan |= bin_commit<XT, B16, Q>(a, x, f0, V, R, tid);
+      }
+      if (has_nan && tid < rows_here) *flag = 1;
+      __syncthreads();
+      return *flag != 0;
+    }
+  }
   for (int f0 = 0; f0 < F; f0 += a.bin_chunk) {
     const int kc = (F - f0) < a.bin_chunk ? (F - f0) : a.bin_chunk;
     __syncthreads();   // temp is free (the previous chunk is searched)
-    constexpr int V = 16 / sizeof(XT);   // elements per 16-byte load
     const bool vec = vec_ok && (f0 % V) == 0 && (kc % V) == 0 && f0 + kc <= C;
     const uint32_t n = (uint32_t)rows_here * (uint32_t)kc;
     const uint32_t ukc = (uint32_t)kc;
@@ -642,27 +766,7 @@ __device__ __forceinline__ bool stage_bins(volatile int* flag, XT* temp, const K
       XT x[Q];
 #pragma unroll
       for (int q = 0; q < Q; ++q) x[q] = temp[(c + q < kc ? c + q : kc - 1) * R + tid];
-      uint32_t b[Q];
-      rank_search<XT, Q>(a, x, f0 + c, b);
-      uint32_t w[Q / P];
-#pragma unroll
-      for (int j = 0; j < Q / P; ++j) w[j] = 0u;
-#pragma unroll
-      for (int q = 0; q < Q; ++q) {
-        const bool nan = x[q] != x[q];
-        has_nan |= nan && (c + q < kc);
-        w[q / P] |= (nan ? BT::kNan : b[q]) << ((q % P) * (32 / P));
-      }
-#pragma unroll
-      for (int j = 0; j < Q / P; ++j) {
-        const int word = (f0 + c) / P + j;
-        if (c + j * P < kc) {
-          __attribute__((address_space(3))) uint32_t* dst =
-              reinterpret_cast<__attribute__((address_space(3))) uint32_t*>(
-                  static_cast<uintptr_t>((uint32_t)(word * R + tid) * 4u));
-          *dst = w[j];
-        }
-      }
+      has_nan |= bin_commit<XT, B16, Q>(a, x, f0 + c, kc - c, R, tid);
     }
   }
   if (has_nan && tid < rows_here) *flag = 1;
@@ -1011,7 +1115,7 @@ __global__ void __launch_bounds__(512) bheap_fix_kernel(const KArgs a) {
     const int i = tid + u * R;
     pf[u] = src[i < n16_all ? i : n16_all - 1];
   }
-  const bool tile_nan = stage_bins<XT, B16, 4 * NG>(
+  const bool tile_nan = stage_bins<XT, B16, 4 * NG, (KMAX <= 4)>(
       flag, reinterpret_cast<XT*>(smem + kFixStage), a, row0, R, tid);
   float acc[KMAX];
   init_acc(acc, a);

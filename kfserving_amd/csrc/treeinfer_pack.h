@@ -489,6 +489,84 @@ void kary_tables(const RankTables<XT>& rt, std::vector<unsigned char>* out, int*
   *height = H;
 }
 
+// Bucket tables (float32 view of the binned heap, rank_search): per feature
+// {lo, scale, first key, 0}, then start[F][NB] u16, then every feature's
+// sorted thresholds followed by 4 +inf.  lo is the smallest threshold, scale =
+// NB / (hi - lo) (0 for a feature with fewer than two thresholds: one bucket),
+// and start[k] counts the thresholds whose ti::bin_bucket is below k -- the
+// same float32 operations the device applies to x, so the thresholds of lower
+// buckets are < x and those of higher buckets >= x for every x, and the 4 keys
+// from start[bucket(x)] on decide the rank.  NB, one per forest, is the first
+// power of two from the largest threshold count up to 4,096 at which no
+// bucket holds more than 4 thresholds.  Returns false, leaving *out alone,
+// when there is none, when 2 gathers are no fewer than the 5-ary tree's
+// (H <= 2), or when a feature's hi - lo overflows or its scale is not a
+// positive finite float.  One load of 4 keys is a measured bound: every bucket
+// gather is divergent, while the 5-ary tree's top three levels sit in a few
+// cache lines, so with 3 loads (C2: 4,794 thresholds in 4,096 buckets, 12 in
+// the fullest) the texture addresser's time doubled and the kernel lost 9 %;
+// with one (c2_hist) it gains 2 %.
+// start[F][NB] at NB buckets and the fullest bucket's count; < 0 when some
+// feature's span or scale is unusable.
+int bucket_starts(const RankTables<float>& rt, int NB, std::vector<float>* ls,
+                  std::vector<uint16_t>* start) {
+  const int F = static_cast<int>(rt.u.size());
+  ls->assign(static_cast<size_t>(F) * 2, 0.0f);
+  start->assign(static_cast<size_t>(F) * NB, 0);
+  std::vector<size_t> cnt;
+  size_t occ_max = 0;
+  for (int f = 0; f < F; ++f) {
+    const std::vector<float>& u = rt.u[f];
+    float lo = 0.0f, scale = 0.0f;
+    if (!u.empty()) lo = u.front();
+    if (u.size() > 1) {
+      const float span = u.back() - lo;
+      scale = static_cast<float>(NB) / span;
+      if (!std::isfinite(span) || !std::isfinite(scale) || !(scale > 0.0f)) return -1;
+    }
+    (*ls)[2 * f] = lo;
+    (*ls)[2 * f + 1] = scale;
+    cnt.assign(NB, 0);
+    for (float t : u) ++cnt[ti::bin_bucket(t, lo, scale, NB)];
+    size_t below = 0;
+    for (int k = 0; k < NB; ++k) {
+      (*start)[static_cast<size_t>(f) * NB + k] = static_cast<uint16_t>(below);
+      below += cnt[k];
+      occ_max = std::max(occ_max, cnt[k]);
+    }
+  }
+  return static_cast<int>(occ_max);
+}
+
+bool bucket_tables(const RankTables<float>& rt, std::vector<unsigned char>* out, int* nb_out) {
+  const int F = static_cast<int>(rt.u.size());
+  if (rt.m_max <= 24) return false;   // the 5-ary tree has H <= 2 levels: two gathers already
+  int NB = 2;
+  while (NB < 4096 && static_cast<size_t>(NB) < rt.m_max) NB *= 2;
+  std::vector<float> ls;
+  std::vector<uint16_t> start;
+  int occ = bucket_starts(rt, NB, &ls, &start);
+  while (occ > 4 && NB < 4096) occ = bucket_starts(rt, NB *= 2, &ls, &start);
+  if (occ < 0 || occ > 4) return false;
+  struct Feat { float lo, scale; uint32_t first, pad; };
+  size_t keys = 0;
+  for (int f = 0; f < F; ++f) keys += rt.u[f].size() + 4;
+  const size_t b_fs = static_cast<size_t>(F) * sizeof(Feat), b_st = start.size() * sizeof(uint16_t);
+  out->assign(b_fs + b_st + keys * sizeof(float), 0);
+  Feat* fs = reinterpret_cast<Feat*>(out->data());
+  std::memcpy(out->data() + b_fs, start.data(), b_st);
+  float* srt = reinterpret_cast<float*>(out->data() + b_fs + b_st);
+  size_t at = 0;
+  for (int f = 0; f < F; ++f) {
+    fs[f] = Feat{ls[2 * f], ls[2 * f + 1], static_cast<uint32_t>(at), 0u};
+    at = std::copy(rt.u[f].begin(), rt.u[f].end(), srt + at) - srt;
+    std::fill(srt + at, srt + at + 4, INFINITY);
+    at += 4;
+  }
+  *nb_out = NB;
+  return true;
+}
+
 // The fixed walk (bheap_fix_kernel) finds a node's children pair through the
 // pair slot the node word carries in bits 3..10, not by heap arithmetic, so
 // within a level the slots may be any permutation.  fix_permute numbers each
@@ -497,8 +575,11 @@ void kary_tables(const RankTables<XT>& rt, std::vector<unsigned char>* out, int*
 // level's slots -- the same address (a broadcast) or nearby dwords -- instead
 // of pairs up to 1 KB apart whose dwords collide in the LDS banks.  Same
 // words, same walk, same sums; only the fixed walk reads this image (leaf ids
-// keep the heap-indexed walk on img).
-void fix_permute(BinImage* bi, const std::vector<double>& hcov, int NE) {
+// keep the heap-indexed walk on img).  `spread` (the default; TI_FIX_SPREAD=0
+// numbers every level sequentially) balances the levels of more than 32 pairs
+// over the bank classes, below.
+void fix_permute(BinImage* bi, const std::vector<double>& hcov, int NE, bool spread) {
+  constexpr int kCls = 32;   // pair slots per sweep of the 64 LDS banks
   const int64_t T = static_cast<int64_t>(bi->img.size()) / bi->stride;
   bi->fix_img.assign(bi->img.size(), 0);
   std::vector<int32_t> pi(NE, 0), lvl;
@@ -512,7 +593,25 @@ void fix_permute(BinImage* bi, const std::vector<double>& hcov, int NE) {
       lvl.resize(lo);
       for (int i = 0; i < lo; ++i) lvl[i] = lo + i;
       std::stable_sort(lvl.begin(), lvl.end(), [c](int32_t x, int32_t y) { return c[x] > c[y]; });
-      for (int i = 0; i < lo; ++i) pi[lvl[i]] = lo + i;
+      if (!spread || lo <= kCls) {
+        for (int i = 0; i < lo; ++i) pi[lvl[i]] = lo + i;
+        continue;
+      }
+      // more than 32 pairs: slot s lies in bank class s % 32 (32 pairs of 8 B
+      // span the 64 banks).  Sequential numbering gives class k the ranks k,
+      // k + 32, k + 64 ...: the hottest node of each block of 32.  Instead
+      // each node, hottest first, takes the class with the least cover so far
+      // that still has room, so the classes carry equal traffic
+      double load[kCls] = {0};
+      int used[kCls] = {0};
+      for (int i = 0; i < lo; ++i) {
+        int k = -1;
+        for (int b = 0; b < kCls; ++b)
+          if (used[b] < lo / kCls && (k < 0 || load[b] < load[k])) k = b;
+        pi[lvl[i]] = lo + k + kCls * used[k];
+        load[k] += c[lvl[i]];
+        ++used[k];
+      }
     }
     auto relabel = [&](uint32_t w, int h) { return (w & ~0x7F8u) | (static_cast<uint32_t>(pi[h]) << 3); };
     nn[1] = relabel(on[1], 1);
@@ -549,8 +648,13 @@ bool pack_bheap(const ti_forest_desc* d, int D, BinImage* out,
   bi->L = rt.L;
   bi->kary = 0;
   if constexpr (sizeof(XT) == 4) {
-    if (env_int("TI_KARY", 1) != 0) kary_tables(rt, &bi->tbl, &bi->kary);
-    else eytzinger_tables(rt, &bi->tbl);
+    // bucket-first search in place of the 5-ary one unless it would be no
+    // shorter (TI_BIN_BUCKETS=0: never; TI_KARY=0 still means Eytzinger)
+    const bool kary = env_int("TI_KARY", 1) != 0;
+    const bool bkt = kary && env_int("TI_BIN_BUCKETS", 1) != 0 &&
+                     bucket_tables(rt, &bi->tbl, &bi->bkt_nb);
+    if (!bkt && kary) kary_tables(rt, &bi->tbl, &bi->kary);
+    if (!bkt && !kary) eytzinger_tables(rt, &bi->tbl);
   } else {
     eytzinger_tables(rt, &bi->tbl);
   }
@@ -610,7 +714,7 @@ bool pack_bheap(const ti_forest_desc* d, int D, BinImage* out,
       }
     }
   }
-  if (perm) fix_permute(bi, hcov, NE);
+  if (perm) fix_permute(bi, hcov, NE, env_int("TI_FIX_SPREAD", 1) != 0);
   *out = std::move(image);
   return true;
 }
