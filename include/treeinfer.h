@@ -129,7 +129,8 @@ extern "C" {
 #define TI_OUTPUT_LEAF     2  /* library leaf id per tree (int32), [rows, T]   */
 #define TI_OUTPUT_CONTRIB  3  /* TreeSHAP contributions, [rows, K * (F + 1)]:  */
                               /* per group F feature columns, then the bias     */
-                              /* (xgboost pred_contribs); needs desc.cover      */
+                              /* (xgboost pred_contribs); needs desc.cover, no  */
+                              /* TI_NODE_CAT_XGB node and no linear leaves      */
 
 /*
  * Canonical forest: host structure-of-arrays over the nodes of all trees,
@@ -171,7 +172,11 @@ typedef struct ti_forest_desc {
   /* node covers (ABI 3): the child weights of TreeSHAP (xgboost sum_hess,
    * LightGBM internal/leaf counts, sklearn weighted_n_node_samples); NULL when
    * the model file has none -- TI_OUTPUT_CONTRIB is then unsupported.  Replaces
-   * XGBoosterPredict(option_mask = pred_contribs) / LGBM predict_type = 3. */
+   * XGBoosterPredict(option_mask = pred_contribs) / LGBM predict_type = 3.
+   * Contributions cover numerical splits and categorical splits with
+   * LightGBM's rule (the hot child is the one the rule above picks, as
+   * Tree::TreeSHAP does through Decision); a forest with a TI_NODE_CAT_XGB
+   * node or with linear leaves is TI_ERR_UNSUPPORTED for TI_OUTPUT_CONTRIB. */
   const double*  cover;       /* [N]                                                */
   /* linear leaves (ABI 6); NULL / 0 when the forest has none.  CSR over the
    * nodes, internal nodes own empty ranges.  Replaces leaf_const / leaf_features

@@ -39,7 +39,9 @@ using ti::KernelFn;
 // feature seen again is unwound and re-extended at the end, so elements are
 // in order of last occurrence).  An element holds the product of the
 // child/parent cover ratios of its splits (zero fraction) and the condition
-// a row must meet to follow all of them (one fraction 1, else 0).
+// a row must meet to follow all of them (one fraction 1, else 0): an interval
+// with the NaN / zero flags for its numerical splits and, under kShapCat, a
+// set of category codes for its LightGBM categorical splits (ShapCatRef).
 struct ShapPath {
   int32_t group;    // output group (leaf_width 1)
   int32_t n;        // elements (excluding the root's dummy element)
@@ -49,12 +51,26 @@ struct ShapPath {
 constexpr uint32_t kShapNanOk = 1u;    // NaN follows every split of the element
 constexpr uint32_t kShapZeroOk = 2u;   // exact 0 follows every split (LightGBM zero rule)
 constexpr uint32_t kShapEmpty = 4u;    // no non-NaN value follows (a left turn at a NaN threshold)
+constexpr uint32_t kShapCat = 8u;      // some split of the element is categorical: the row must
+                                       //   also pass the set test (shap_cat_refs[element])
+constexpr uint32_t kShapCatOutside = 16u;   // a value no bit of the set covers follows (NaN,
+                                       //   x <= -1, x >= 2^31, a code past the last word): the
+                                       //   path turns right at every categorical split
 struct ShapElem {
   int32_t feature;
   uint32_t flags;
   double lo;        // follows iff lo < x <= hi (non-NaN, non-zero x)
   double hi;
   double zf;        // zero fraction
+};
+static_assert(sizeof(ShapElem) == 32, "ShapElem is scalar-loaded as 32 bytes");
+// The category set `allow` of a kShapCat element: words [first, first +
+// nwords) of the forest's shap_cat_words; bit v % 32 of word v / 32 set iff
+// code v follows every categorical split of the element.  One per element
+// (zeros where kShapCat is clear), in forests with categorical nodes only.
+struct alignas(8) ShapCatRef {   // one 8-byte scalar load
+  uint32_t first;
+  uint32_t nwords;
 };
 
 namespace {
@@ -248,6 +264,8 @@ struct ShapPtrs {
   ShapElem* shap_elems = nullptr;
   double* shap_leaf = nullptr;
   double* shap_bias = nullptr;
+  ShapCatRef* shap_cat_refs = nullptr;   // [elements], forests with categorical nodes only
+  uint32_t* shap_cat_words = nullptr;    //   the elements' category sets
   void* shap_tab = nullptr;          // TreeSHAP coefficient table (shap_table_kernel), MT-typed
   int64_t* shap_tab_off = nullptr;   // [paths] first coefficient of each path
 };
@@ -410,11 +428,12 @@ struct ti_forest {
   uint32_t tx16_mask = 0;          //   u16: the bottom word's bin-offset bits (KArgs bin_mask)
   // ---- the packed arrays, until every replica is resident
   std::unique_ptr<HostImage> host;
-  // TreeSHAP (TI_OUTPUT_CONTRIB); has_shap = 0 when the forest has no covers.
+  // TreeSHAP (TI_OUTPUT_CONTRIB); has_shap = 0 when the forest has no covers
+  // (shap_refused = 1) or a categorical node with XGBoost's rule (2).
   // The path tables are built and uploaded on the first contributions call
   // (ensure_shap), from a host copy of the arrays they need, so predict-only
   // serving never pays for them.
-  int32_t has_shap = 0, shap_maxl = 0;
+  int32_t has_shap = 0, shap_refused = 0, shap_maxl = 0;
   int64_t shap_npaths = 0;
   std::atomic<bool> shap_ready{false};
   std::mutex shap_mu;
@@ -424,6 +443,9 @@ struct ti_forest {
     std::vector<int32_t> tree_group, feature, left, right;
     std::vector<double> threshold, leaf_value, base_margin, cover;
     std::vector<uint8_t> flags;
+    std::vector<uint32_t> cat_bits;      // all n_cat_words (a tree subset keeps them whole)
+    std::vector<int64_t> cat_offset;
+    std::vector<int32_t> cat_nwords;
   };
   std::unique_ptr<ShapSource> shap_src;
   std::vector<ShapPath> h_paths;
@@ -443,6 +465,8 @@ struct ti_forest {
   std::atomic<int32_t> host_register{env_int("TI_HOST_REGISTER", 0) != 0 ? 1 : 0};
   double shap_tab_build_ms = 0.0;   // the last table build (slot's shap_table_kernel + upload)
   std::vector<ShapElem> h_elems;
+  std::vector<ShapCatRef> h_shap_cat_refs;   // parallel to h_elems, or empty
+  std::vector<uint32_t> h_shap_cat;          // the category sets of all paths
   std::vector<double> h_path_leaf, h_shap_bias;
   std::atomic<int64_t> lin_scratch_mb{1024};   // TI_OPT_LINEAR_SCRATCH_MB
   std::vector<std::unique_ptr<DeviceForest>> devs;

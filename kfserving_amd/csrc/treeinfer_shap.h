@@ -7,6 +7,43 @@
 #include "treeinfer_forest.h"
 
 
+// Whether value x (the zero map applied) follows every split of a path
+// element: the interval and the NaN / zero flags of its numerical splits
+// (shap_follow_num) and, under kShapCat, membership of its category set
+// (shap_follow_cat); shap_follow is both.  The element comes through scalar
+// loads, so the flag test is a scalar branch; the set's {first, nwords} is one
+// scalar load too and only the set's word is per lane.
+__device__ __forceinline__ bool shap_follow_num(const ShapElem& e, double x) {
+  if (x != x) return (e.flags & kShapNanOk) != 0;
+  if (x == 0.0) return (e.flags & kShapZeroOk) != 0;
+  return !(e.flags & kShapEmpty) && e.lo < x && x <= e.hi;
+}
+
+// LightGBM's rule (ti::cat_left) against the element's set: codes are trunc(x)
+// for x in (-1, 2^31); anything else, and a code past the set's last word,
+// follows iff the path never turned left (kShapCatOutside).  The zero map
+// cannot change the answer: |x| <= 1e-35 is code 0 either way.
+__device__ __forceinline__ bool shap_follow_cat(uint32_t flags, double x, int64_t ei,
+                                                const ShapCatRef* __restrict__ cat_refs,
+                                                const uint32_t* __restrict__ cat_words) {
+  // both fields in one load, ahead of the divergent part below
+  const uint64_t rw = *reinterpret_cast<const uint64_t*>(cat_refs + ei);
+  const ShapCatRef r{static_cast<uint32_t>(rw), static_cast<uint32_t>(rw >> 32)};
+  const bool inside = x > -1.0 && x < 2147483648.0;
+  const uint32_t v = inside ? static_cast<uint32_t>(x) : 0u;
+  const bool covered = inside && (v >> 5) < r.nwords;
+  const uint32_t word = covered ? cat_words[r.first + (v >> 5)] : 0u;
+  return covered ? ((word >> (v & 31u)) & 1u) != 0u : (flags & kShapCatOutside) != 0;
+}
+
+__device__ __forceinline__ bool shap_follow(const ShapElem& e, double x, int64_t ei,
+                                            const ShapCatRef* __restrict__ cat_refs,
+                                            const uint32_t* __restrict__ cat_words) {
+  bool follow = shap_follow_num(e, x);
+  if (e.flags & kShapCat) follow = shap_follow_cat(e.flags, x, ei, cat_refs, cat_words) && follow;
+  return follow;
+}
+
 // One row per lane (64-row blocks).  Per path: the one fractions of the
 // row, then the path weights extended from scratch (ExtendPath) and, per
 // element, the unwound sum (UnwoundPathSum) times (one - zero) times the
@@ -20,7 +57,8 @@ __global__ void __launch_bounds__(64) contrib_kernel(
     const ShapPath* __restrict__ paths, int64_t n_paths, const ShapElem* __restrict__ elems,
     const double* __restrict__ leafv, int32_t LW, int32_t K, int32_t F, int32_t maxl,
     const double* __restrict__ bias, double divisor, double* __restrict__ acc,
-    ACC* __restrict__ out) {
+    ACC* __restrict__ out, const ShapCatRef* __restrict__ cat_refs,
+    const uint32_t* __restrict__ cat_words) {
   extern __shared__ double shap_lds[];
   const int lane = threadIdx.x;
   const int64_t row = (int64_t)blockIdx.x * 64 + lane;
@@ -37,10 +75,7 @@ __global__ void __launch_bounds__(64) contrib_kernel(
       const ShapElem e = elems[P.first + i];
       double x = e.feature < cols ? (double)xr[e.feature] : __builtin_nan("");
       if (zero_map_on && __builtin_fabs(x) <= (double)1e-35f) x = 0.0;
-      bool follow;
-      if (x != x) follow = (e.flags & kShapNanOk) != 0;
-      else if (x == 0.0) follow = (e.flags & kShapZeroOk) != 0;
-      else follow = !(e.flags & kShapEmpty) && e.lo < x && x <= e.hi;
+      const bool follow = shap_follow(e, x, P.first + i, cat_refs, cat_words);
       ob[i * 64 + lane] = follow ? 1.0 : 0.0;
     }
     w[lane] = 1.0;
@@ -123,7 +158,8 @@ __global__ void __launch_bounds__(64) contrib_reg_kernel(
     const double* __restrict__ leafv, int32_t LW, int32_t K, int32_t F, int32_t maxl,
     const double* __restrict__ bias, double divisor, double* __restrict__ part,
     int64_t paths_per_slice, ACC* __restrict__ out, const MT* __restrict__ tab,
-    const int64_t* __restrict__ tab_off) {
+    const int64_t* __restrict__ tab_off, const ShapCatRef* __restrict__ cat_refs,
+    const uint32_t* __restrict__ cat_words) {
   (void)maxl;
   extern __shared__ double shap_lds[];
   const int lane = threadIdx.x;
@@ -144,11 +180,19 @@ __global__ void __launch_bounds__(64) contrib_reg_kernel(
       const ShapElem e = pe[i];
       double x = e.feature < cols ? (double)xr[e.feature] : __builtin_nan("");
       if (zero_map_on && __builtin_fabs(x) <= (double)1e-35f) x = 0.0;
-      bool follow;
-      if (x != x) follow = (e.flags & kShapNanOk) != 0;
-      else if (x == 0.0) follow = (e.flags & kShapZeroOk) != 0;
-      else follow = !(e.flags & kShapEmpty) && e.lo < x && x <= e.hi;
-      om |= (follow ? 1u : 0u) << i;
+      om |= (shap_follow_num(e, x) ? 1u : 0u) << i;
+    }
+    if (cat_refs) {
+      // A forest with categorical nodes (one scalar branch a path; the others
+      // run the loop above alone): clear the bits of the elements whose
+      // category set the row is not in.
+      for (int i = 0; i < n; ++i) {
+        const int32_t fe = pe[i].feature;
+        const uint32_t fl = pe[i].flags;
+        if (!(fl & kShapCat)) continue;
+        const double x = fe < cols ? (double)xr[fe] : __builtin_nan("");
+        if (!shap_follow_cat(fl, x, P.first + i, cat_refs, cat_words)) om &= ~(1u << i);
+      }
     }
     if constexpr (TAB) {
       // the pattern's coefficients: kShapTabStride values, 32- or 64-byte
@@ -402,13 +446,48 @@ void free_shap(DeviceForest& d) {
 }
 
 // TreeSHAP path tables + bias (see ShapPath).  Forests without covers or
-// with categorical splits get none (TI_OUTPUT_CONTRIB is then unsupported).
+// with XGBoost-rule categorical splits get none (TI_OUTPUT_CONTRIB is then
+// unsupported).
+//
+// The categorical part of an element is a set of codes `allow` (words, bit
+// v % 32 of word v / 32) plus kShapCatOutside, which says what happens to
+// every value the words do not cover.  Before the first categorical split
+// the element allows everything: no words, outside set.  With S the node's
+// bitset (LightGBM's rule: in S -> left; NaN, x <= -1, x >= 2^31 and codes
+// past S's last word -> right):
+//   right turn: allow \= S.  Nothing outside S's words is lost, so the words
+//               grow to max(own, S's) while outside is set, and stay otherwise.
+//   left turn:  allow &= S.  Nothing past S's words follows: the words are cut
+//               to S's length (words the set did not have yet are S's own
+//               where outside was set, nothing otherwise) and outside clears.
+// A set may end up empty with outside clear: an element no row follows.
 struct ShapBuilder {
+  struct Elem {
+    ShapElem e;
+    std::vector<uint32_t> allow;   // kShapCat elements only
+  };
   const ti_forest_desc* d;
   ti_forest* f;
   int64_t b = 0;
   int group = 0;
-  std::vector<ShapElem> cur;
+  std::vector<Elem> cur;
+
+  static void cat_turn(Elem& el, const uint32_t* s, size_t ns, bool left) {
+    const bool outside = !(el.e.flags & kShapCat) || (el.e.flags & kShapCatOutside);
+    const uint32_t fill = outside ? ~0u : 0u;
+    std::vector<uint32_t>& a = el.allow;
+    const size_t len = a.size();
+    if (left) {
+      a.resize(outside ? ns : std::min(len, ns), fill);
+      for (size_t w = 0; w < a.size(); ++w) a[w] &= s[w];
+      el.e.flags &= ~kShapCatOutside;
+    } else {
+      if (outside) a.resize(std::max(len, ns), fill);
+      for (size_t w = 0; w < std::min(a.size(), ns); ++w) a[w] &= ~s[w];
+      if (outside) el.e.flags |= kShapCatOutside;
+    }
+    el.e.flags |= kShapCat;
+  }
 
   void dfs(int32_t v) {
     const int64_t g = b + v;
@@ -419,7 +498,13 @@ struct ShapBuilder {
       p.n = static_cast<int32_t>(cur.size());
       p.first = static_cast<int64_t>(f->h_elems.size());
       p.leaf = static_cast<int64_t>(f->h_path_leaf.size()) / LW;
-      f->h_elems.insert(f->h_elems.end(), cur.begin(), cur.end());
+      for (const Elem& el : cur) {
+        f->h_elems.push_back(el.e);
+        if (!f->has_cat) continue;   // no categorical node in the forest: no refs at all
+        f->h_shap_cat_refs.push_back(ShapCatRef{static_cast<uint32_t>(f->h_shap_cat.size()),
+                                                static_cast<uint32_t>(el.allow.size())});
+        f->h_shap_cat.insert(f->h_shap_cat.end(), el.allow.begin(), el.allow.end());
+      }
       for (int k = 0; k < LW; ++k) f->h_path_leaf.push_back(d->leaf_value[g * LW + k]);
       f->h_paths.push_back(p);
       f->shap_maxl = std::max(f->shap_maxl, p.n);
@@ -427,29 +512,36 @@ struct ShapBuilder {
     }
     const int32_t fe = d->feature[g];
     const double t = d->threshold[g];
+    const bool cat = (d->flags[g] & TI_NODE_CATEGORICAL) != 0;
     const bool nan_left = (d->flags[g] & TI_NODE_NAN_LEFT) != 0;
     const bool zero_left = (d->flags[g] & TI_NODE_ZERO_FLIP) ? !(0 <= t) : (0 <= t);
     for (int side = 0; side < 2; ++side) {
       const bool left = side == 0;
       const int32_t child = left ? d->left[g] : d->right[g];
-      const std::vector<ShapElem> saved = cur;
-      ShapElem e{fe, kShapNanOk | kShapZeroOk, -INFINITY, INFINITY, 1.0};
+      const std::vector<Elem> saved = cur;
+      Elem el{ShapElem{fe, kShapNanOk | kShapZeroOk, -INFINITY, INFINITY, 1.0}, {}};
       for (size_t i = 0; i < cur.size(); ++i)
-        if (cur[i].feature == fe) {   // unwind the earlier split on fe, re-extend at the end
-          e = cur[i];
+        if (cur[i].e.feature == fe) {   // unwind the earlier split on fe (interval and set),
+          el = cur[i];                  // re-extend at the end
           cur.erase(cur.begin() + static_cast<std::ptrdiff_t>(i));
           break;
         }
+      ShapElem& e = el.e;
       e.zf = (d->cover[b + child] / d->cover[g]) * e.zf;
-      if (left) {
-        if (std::isnan(t)) e.flags |= kShapEmpty;
-        else e.hi = std::min(e.hi, t);
-      } else if (!std::isnan(t)) {
-        e.lo = std::max(e.lo, t);
+      if (cat) {
+        // the interval and the NaN / zero flags belong to the numerical splits
+        cat_turn(el, d->cat_bits + d->cat_offset[g], static_cast<size_t>(d->cat_nwords[g]), left);
+      } else {
+        if (left) {
+          if (std::isnan(t)) e.flags |= kShapEmpty;
+          else e.hi = std::min(e.hi, t);
+        } else if (!std::isnan(t)) {
+          e.lo = std::max(e.lo, t);
+        }
+        if (nan_left != left) e.flags &= ~kShapNanOk;
+        if (zero_left != left) e.flags &= ~kShapZeroOk;
       }
-      if (nan_left != left) e.flags &= ~kShapNanOk;
-      if (zero_left != left) e.flags &= ~kShapZeroOk;
-      cur.push_back(e);
+      cur.push_back(std::move(el));
       dfs(child);
       cur = saved;
     }
@@ -471,12 +563,17 @@ struct ShapBuilder {
   }
 };
 
-// At create: whether contributions are possible (covers, no categorical
-// splits), and the host copy build_shap will read on first use.
+// At create: whether contributions are possible (covers; categorical nodes
+// all with LightGBM's rule), and the host copy build_shap will read on first
+// use.  The element's category set is LightGBM's membership test; a forest
+// with an XGBoost-rule node (TI_NODE_CAT_XGB: in the set -> right, invalid
+// codes left, NaN by flag) is refused.
 void keep_shap_source(const ti_forest_desc* d, ti_forest* f) {
+  f->shap_refused = 1;
   if (!d->cover) return;
-  for (int64_t g = 0; g < d->n_nodes; ++g)
-    if (d->feature[g] >= 0 && (d->flags[g] & TI_NODE_CATEGORICAL)) return;
+  f->shap_refused = 2;
+  if (f->has_cat_xgb) return;
+  f->shap_refused = 0;
   auto src = std::make_unique<ti_forest::ShapSource>();
   const int64_t N = d->n_nodes, T = d->n_trees;
   src->tree_offset.assign(d->tree_offset, d->tree_offset + T + 1);
@@ -504,6 +601,14 @@ void keep_shap_source(const ti_forest_desc* d, ti_forest* f) {
   src->desc.cat_bits = nullptr;
   src->desc.cat_offset = nullptr;
   src->desc.cat_nwords = nullptr;
+  if (f->has_cat) {   // the bitsets whole: a tree subset's offsets still point into them
+    src->cat_bits.assign(d->cat_bits, d->cat_bits + d->n_cat_words);
+    src->cat_offset.assign(d->cat_offset, d->cat_offset + N);
+    src->cat_nwords.assign(d->cat_nwords, d->cat_nwords + N);
+    src->desc.cat_bits = src->cat_bits.data();
+    src->desc.cat_offset = src->cat_offset.data();
+    src->desc.cat_nwords = src->cat_nwords.data();
+  }
   f->shap_src = std::move(src);
   f->has_shap = 1;
 }
@@ -540,6 +645,8 @@ int ensure_shap(ti_forest* f) {
   std::lock_guard<std::mutex> lk(f->shap_mu);
   if (f->shap_ready.load(std::memory_order_relaxed)) return TI_OK;
   if (f->h_paths.empty()) build_shap(&f->shap_src->desc, f);
+  if (f->h_shap_cat.size() > std::numeric_limits<uint32_t>::max())
+    return fail(TI_ERR_UNSUPPORTED, "the category sets of the TreeSHAP paths exceed 2^32 words");
   // the coefficient table's shape (contrib_reg_kernel TAB): paths of <= 8
   // unique features, 2^n x 8 coefficients each (padded), in the path
   // arithmetic's type.  The table itself is built per replica, later, by
@@ -571,7 +678,9 @@ int ensure_shap(ti_forest* f) {
     if ((rc = upload(&d.shap_mem, &d.shap_paths, f->h_paths, &d.bytes)) ||
         (rc = upload(&d.shap_mem, &d.shap_elems, f->h_elems, &d.bytes)) ||
         (rc = upload(&d.shap_mem, &d.shap_leaf, f->h_path_leaf, &d.bytes)) ||
-        (rc = upload(&d.shap_mem, &d.shap_bias, f->h_shap_bias, &d.bytes)))
+        (rc = upload(&d.shap_mem, &d.shap_bias, f->h_shap_bias, &d.bytes)) ||
+        (rc = upload(&d.shap_mem, &d.shap_cat_refs, f->h_shap_cat_refs, &d.bytes)) ||
+        (rc = upload(&d.shap_mem, &d.shap_cat_words, f->h_shap_cat, &d.bytes)))
       break;
   }
   if (rc) {
@@ -591,6 +700,8 @@ int ensure_shap(ti_forest* f) {
   f->h_paths.clear(); f->h_paths.shrink_to_fit();
   f->h_elems.clear(); f->h_elems.shrink_to_fit();
   f->h_path_leaf.clear(); f->h_path_leaf.shrink_to_fit();
+  f->h_shap_cat_refs.clear(); f->h_shap_cat_refs.shrink_to_fit();
+  f->h_shap_cat.clear(); f->h_shap_cat.shrink_to_fit();
   f->shap_src.reset();
   f->shap_ready.store(true, std::memory_order_release);
   return TI_OK;
@@ -648,7 +759,10 @@ int launch_contrib(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_
                    int32_t cols, int64_t stride, void* out, hipStream_t stream) {
   if (!f->has_shap)
     return fail(TI_ERR_UNSUPPORTED,
-                "contributions need node covers (ti_forest_desc.cover) and no categorical splits");
+                f->shap_refused == 2
+                    ? "contributions of categorical splits with XGBoost's rule (TI_NODE_CAT_XGB) are "
+                      "not supported; categorical splits with LightGBM's rule are"
+                    : "contributions need node covers (ti_forest_desc.cover)");
   {
     const int rc = ensure_shap(f);
     if (rc) return rc;
@@ -699,14 +813,16 @@ int launch_contrib(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_
                          static_cast<const XT_*>(X), rows, stride, cols, f->lgb_zero_map,      \
                          d.shap_paths, n_paths, d.shap_elems, d.shap_leaf, f->LW, f->K, f->F,  \
                          f->shap_maxl, d.shap_bias, f->divisor, part, pps, static_cast<ACC_*>(out), \
-                         static_cast<const MT_*>(d.shap_tab), d.shap_tab_off);                 \
+                         static_cast<const MT_*>(d.shap_tab), d.shap_tab_off,                  \
+                         d.shap_cat_refs, d.shap_cat_words);                                   \
     else                                                                                       \
       hipLaunchKernelGGL((contrib_reg_kernel<XT_, ACC_, MT_, N_>), dim3(grid_r, (unsigned)slices), dim3(64), \
                          lds_w, stream,                                                        \
                          static_cast<const XT_*>(X), rows, stride, cols, f->lgb_zero_map,      \
                          d.shap_paths, n_paths, d.shap_elems, d.shap_leaf, f->LW, f->K, f->F,  \
                          f->shap_maxl, d.shap_bias, f->divisor, part, pps, static_cast<ACC_*>(out), \
-                         static_cast<const MT_*>(nullptr), static_cast<const int64_t*>(nullptr)); \
+                         static_cast<const MT_*>(nullptr), static_cast<const int64_t*>(nullptr), \
+                         d.shap_cat_refs, d.shap_cat_words);                                   \
     if (part) {                                                                                \
       const unsigned g2 = static_cast<unsigned>((rows + 255) / 256);                           \
       hipLaunchKernelGGL((contrib_slices_kernel<ACC_>), dim3(g2), dim3(256), 0, stream, part,  \
@@ -763,23 +879,27 @@ int launch_contrib(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_
       hipLaunchKernelGGL((contrib_kernel<float, double>), dim3(grid), dim3(64), lds, stream,
                          static_cast<const float*>(X), rows, stride, cols, f->lgb_zero_map,
                          d.shap_paths, n_paths, d.shap_elems, d.shap_leaf, f->LW, f->K, f->F,
-                         f->shap_maxl, d.shap_bias, f->divisor, acc, static_cast<double*>(out));
+                         f->shap_maxl, d.shap_bias, f->divisor, acc, static_cast<double*>(out),
+                         d.shap_cat_refs, d.shap_cat_words);
     else
       hipLaunchKernelGGL((contrib_kernel<float, float>), dim3(grid), dim3(64), lds, stream,
                          static_cast<const float*>(X), rows, stride, cols, f->lgb_zero_map,
                          d.shap_paths, n_paths, d.shap_elems, d.shap_leaf, f->LW, f->K, f->F,
-                         f->shap_maxl, d.shap_bias, f->divisor, acc, static_cast<float*>(out));
+                         f->shap_maxl, d.shap_bias, f->divisor, acc, static_cast<float*>(out),
+                         d.shap_cat_refs, d.shap_cat_words);
   } else {
     if (f->accum == TI_F64)
       hipLaunchKernelGGL((contrib_kernel<double, double>), dim3(grid), dim3(64), lds, stream,
                          static_cast<const double*>(X), rows, stride, cols, f->lgb_zero_map,
                          d.shap_paths, n_paths, d.shap_elems, d.shap_leaf, f->LW, f->K, f->F,
-                         f->shap_maxl, d.shap_bias, f->divisor, acc, static_cast<double*>(out));
+                         f->shap_maxl, d.shap_bias, f->divisor, acc, static_cast<double*>(out),
+                         d.shap_cat_refs, d.shap_cat_words);
     else
       hipLaunchKernelGGL((contrib_kernel<double, float>), dim3(grid), dim3(64), lds, stream,
                          static_cast<const double*>(X), rows, stride, cols, f->lgb_zero_map,
                          d.shap_paths, n_paths, d.shap_elems, d.shap_leaf, f->LW, f->K, f->F,
-                         f->shap_maxl, d.shap_bias, f->divisor, acc, static_cast<float*>(out));
+                         f->shap_maxl, d.shap_bias, f->divisor, acc, static_cast<float*>(out),
+                         d.shap_cat_refs, d.shap_cat_words);
   }
   TI_HIP(hipGetLastError());
   if (acc != out) TI_HIP(hipFreeAsync(acc, stream));
