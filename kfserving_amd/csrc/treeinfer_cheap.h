@@ -2,7 +2,7 @@
 //
 // heap_predict_kernel (treeinfer_kernels.h) for forests with categorical
 // splits: the same complete-tree records, staged into LDS the same way
-// (prefetch_stage / commit_stage), with each tree's bitsets inside its block:
+// (FixedSpan, stage_step), with each tree's bitsets inside its block:
 //
 //   [2^D - 1 HeapNode<XT>][2^D * leaf_width ACC][bitset words (u32)]
 //
@@ -137,47 +137,29 @@ __device__ __forceinline__ void cheap_stage(const KArgs& a, const unsigned char*
 template <typename XT, typename ACC, int KMAX, bool ZERO, bool XGB>
 __global__ void __launch_bounds__(512) cheap_predict_kernel(const KArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int R = blockDim.x;
-  const int tid = threadIdx.x;
-  const int64_t row0 = (int64_t)blockIdx.x * R;
-  const int64_t row = row0 + tid;
-  const bool live = row < a.n_rows;
-  const size_t feat_bytes = align16((size_t)a.n_features * R * sizeof(XT));
-  volatile int* flag = reinterpret_cast<volatile int*>(smem + feat_bytes);
+  Tile t = one_lane_tile(a, (uint32_t)sizeof(XT));
+  const size_t feat_bytes = align16((size_t)a.n_features * t.R * sizeof(XT));
+  t.flag = reinterpret_cast<volatile int*>(smem + feat_bytes);
   unsigned char* stage = smem + feat_bytes + 16;
-  const uint32_t lane_off = (uint32_t)tid * (uint32_t)sizeof(XT);
-  const bool tile_nan = stage_features<XT>(reinterpret_cast<XT*>(smem), flag, a, row0, R, tid);
-  const int T = a.n_trees;
-  const int S = a.stage_trees;
-  const int64_t stride = a.tree_stride;
+  const bool tile_nan =
+      stage_features<XT>(reinterpret_cast<XT*>(smem), t.flag, a, t.row0, t.R, t.tid);
 
   ACC acc[KMAX];
   init_acc(acc, a);
 
-  // stages as in heap_predict_kernel: stage k covers trees [k*S, min(T, (k+1)*S)),
-  // the next one is in flight in registers while this one is walked
-  const int last0 = ((T - 1) / S) * S;
+  // stages as in heap_predict_kernel
+  const FixedSpan sp(a);
   u32x4 pf[kPf];
-  prefetch_stage(pf, reinterpret_cast<const u32x4*>(a.trees),
-                 (int)(((int64_t)(T < S ? T : S) * stride) >> 4), tid, R);
-  for (int t0 = 0; t0 < T; t0 += S) {
-    const int cnt = (T - t0) < S ? (T - t0) : S;
-    __syncthreads();   // previous stage fully consumed (first pass: features staged)
-    commit_stage(pf, reinterpret_cast<u32x4*>(stage), (int)(((int64_t)cnt * stride) >> 4), tid, R);
-    __syncthreads();
-    {
-      const int tn = t0 + S <= last0 ? t0 + S : last0;
-      const int cn = (T - tn) < S ? (T - tn) : S;
-      prefetch_stage(pf, reinterpret_cast<const u32x4*>(a.trees + (int64_t)tn * stride),
-                     (int)(((int64_t)cn * stride) >> 4), tid, R);
-    }
-    if (tile_nan)
-      cheap_stage<XT, ACC, KMAX, ZERO, XGB, true>(a, stage, cnt, t0, acc, lane_off, row, live);
-    else
-      cheap_stage<XT, ACC, KMAX, ZERO, XGB, false>(a, stage, cnt, t0, acc, lane_off, row, live);
+  stage_first(sp, pf, t.tid, t.R);
+  for (int c = sp.first(); sp.more(c); c = sp.after(c)) {
+    const auto st = stage_step(sp, pf, stage, c, t.tid, t.R);
+    with_flag(tile_nan, [&](auto N) {
+      cheap_stage<XT, ACC, KMAX, ZERO, XGB, decltype(N)::value>(a, stage, st.cnt, st.t0, acc, t.lane_off,
+                                                                t.row, t.live);
+    });
   }
-  if (!live || a.kind == TI_OUTPUT_LEAF) return;
-  finish_row<ACC, KMAX>(acc, a, row);
+  if (!t.live || a.kind == TI_OUTPUT_LEAF) return;
+  finish_row<ACC, KMAX>(acc, a, t.row);
 }
 
 // instantiated in treeinfer_k_cat.hip, selected like every other walk

@@ -28,6 +28,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "treeinfer.h"
 
 #ifndef TI_TILP
@@ -343,27 +345,225 @@ __device__ __forceinline__ void finish_row(const ACC (&acc)[KMAX], const KArgs& 
   }
 }
 
+// ------------------------------------------- what a staged walk is made from
+// The tile of a workgroup: R rows, this thread's row and its part of an LDS
+// image address, and the word of LDS the binning raises its flag in.
+struct Tile {
+  int R, tid;
+  int64_t row0, row;
+  bool live;
+  uint32_t lane_off;
+  volatile int* flag;
+};
+
+// One lane a row: thread tid takes row tid, whose column of an image starts
+// lane_bytes * tid into it.  The flag word follows the tile's image, whose
+// size is the kernel's to say: it sets t.flag (bin_tile: a bin image).
+__device__ __forceinline__ Tile one_lane_tile(const KArgs& a, uint32_t lane_bytes) {
+  Tile t;
+  t.R = blockDim.x;
+  t.tid = threadIdx.x;
+  t.row0 = (int64_t)blockIdx.x * t.R;
+  t.row = t.row0 + t.tid;
+  t.live = t.row < a.n_rows;
+  t.flag = nullptr;
+  t.lane_off = (uint32_t)t.tid * lane_bytes;
+  return t;
+}
+// ... of a bin image ([word][R] of u32)
+__device__ __forceinline__ Tile bin_tile(const KArgs& a, unsigned char* smem) {
+  Tile t = one_lane_tile(a, 4u);
+  t.flag = reinterpret_cast<volatile int*>(smem + (size_t)a.bin_words * t.R * 4);
+  return t;
+}
+
+// Runtime flags of a tile (it holds a NaN; leaf values sit in the records) to
+// template arguments: f is called with std::bool_constants, as
+// treeinfer_dispatch.h's rules call theirs.
+template <typename F>
+__device__ __forceinline__ void with_flag(bool p, F f) {
+  if (p) f(std::true_type{});
+  else f(std::false_type{});
+}
+template <typename F>
+__device__ __forceinline__ void with_flags(bool slow, bool vis, F f) {
+  if (slow) {
+    if (vis) f(std::true_type{}, std::true_type{});
+    else f(std::true_type{}, std::false_type{});
+  } else {
+    if (vis) f(std::false_type{}, std::true_type{});
+    else f(std::false_type{}, std::false_type{});
+  }
+}
+
 // Tree stages move global -> registers -> LDS.  The next stage's loads are
 // issued before the current stage is walked and land in registers while the
 // lanes traverse, so only the LDS write sits between two stages.  A stage is
-// at most kPf * 16 * R bytes (the host sizes it so).
-__device__ __forceinline__ void prefetch_stage(u32x4 (&pf)[kPf], const u32x4* __restrict__ src,
-                                               int n16, int tid, int R) {
+// at most PF * 16 * (copying threads) bytes (the host sizes it so).
+struct CopyN {
   // unconditional loads (index clamped inside the stage): no exec-masked
   // branches, so every load is in flight at once and pf stays in registers
+  template <int PF>
+  static __device__ __forceinline__ void prefetch(u32x4 (&pf)[PF], const u32x4* __restrict__ src,
+                                                  int n16, int tid, int R) {
 #pragma unroll
-  for (int u = 0; u < kPf; ++u) {
-    const int i = tid + u * R;
-    pf[u] = src[i < n16 ? i : n16 - 1];
+    for (int u = 0; u < PF; ++u) {
+      const int i = tid + u * R;
+      pf[u] = src[i < n16 ? i : n16 - 1];
+    }
   }
+  template <int PF>
+  static __device__ __forceinline__ void commit(const u32x4 (&pf)[PF], u32x4* __restrict__ dst,
+                                                int n16, int tid, int R) {
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+      const int i = tid + u * R;
+      if (i < n16) dst[i] = pf[u];
+    }
+  }
+};
+
+// Layout 9's stage copies: as CopyN, but the loads address the uniform base
+// with a 32-bit byte offset (the scalar-base form of global_load: an index
+// clamp and a shift each) and the commit writes every word unconditionally (a
+// clamped lane stores the last word's own value again: no compare and branch
+// per store).  C3 5.41 -> 5.34 ms; the same copies measured about 1 % slower
+// on C2 and C4, which keep the others (profiles/r2_copy_sweep.jsonl).
+struct CopyU {
+  template <int PF>
+  static __device__ __forceinline__ void prefetch(u32x4 (&pf)[PF], const u32x4* __restrict__ src,
+                                                  int n16, int tid, int R) {
+    const unsigned char* base = reinterpret_cast<const unsigned char*>(src);
+    const uint32_t last = (uint32_t)n16 - 1u;
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+      const uint32_t i = (uint32_t)tid + (uint32_t)(u * R);
+      pf[u] = *reinterpret_cast<const u32x4*>(base + (i < last ? i : last) * 16u);
+    }
+  }
+  template <int PF>
+  static __device__ __forceinline__ void commit(const u32x4 (&pf)[PF], u32x4* __restrict__ dst,
+                                                int n16, int tid, int R) {
+    const uint32_t last = (uint32_t)n16 - 1u;
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+      const uint32_t i = (uint32_t)tid + (uint32_t)(u * R);
+      dst[i < last ? i : last] = pf[u];
+    }
+  }
+};
+
+typedef const __attribute__((address_space(4))) uint32_t rx_cu32;   // scalar-loaded tables
+
+// Which trees and which bytes each stage holds.  A span names its stages by a
+// cursor c: first(), more(c), after(c), and following(c), the stage to fetch
+// while c is walked -- the last stage's is itself, so the loop body has no
+// conditional register traffic.  at(c) says what the walk needs of stage c
+// (the span's Stage); fetch / commit copy its words, each span with its copy
+// pair and in its own order of address arithmetic.
+//
+// Stages of S whole records of tree_stride bytes, copied to the start of the
+// stage area: the cursor is the stage's first tree.
+struct FixedSpan {
+  struct Stage { int t0, cnt; };   // trees [t0, t0 + cnt)
+  const unsigned char* trees;
+  int T, S;
+  int64_t stride;
+  __device__ __forceinline__ explicit FixedSpan(const KArgs& a)
+      : trees(a.trees), T(a.n_trees), S(a.stage_trees), stride(a.tree_stride) {}
+  __device__ __forceinline__ int first() const { return 0; }
+  __device__ __forceinline__ bool more(int c) const { return c < T; }
+  __device__ __forceinline__ int after(int c) const { return c + S; }
+  __device__ __forceinline__ int following(int c) const {
+    const int last0 = ((T - 1) / S) * S;   // the last stage
+    return c + S <= last0 ? c + S : last0;
+  }
+  __device__ __forceinline__ int count(int c) const { return (T - c) < S ? (T - c) : S; }
+  __device__ __forceinline__ int n16(int cnt) const { return (int)(((int64_t)cnt * stride) >> 4); }
+  __device__ __forceinline__ Stage at(int c) const { return Stage{c, count(c)}; }
+  template <int PF>
+  __device__ __forceinline__ void fetch(u32x4 (&pf)[PF], int c, int tid, int NT) const {
+    const int cnt = count(c);
+    CopyN::prefetch<PF>(pf, reinterpret_cast<const u32x4*>(trees + (int64_t)c * stride), n16(cnt),
+                        tid, NT);
+  }
+  template <int PF>
+  __device__ __forceinline__ void commit(const u32x4 (&pf)[PF], u32x4* dst, int c, int tid,
+                                         int NT) const {
+    CopyN::commit<PF>(pf, dst, n16(count(c)), tid, NT);
+  }
+};
+
+// Stages of consecutive trees of any size: stage s covers trees
+// [stage_start[s], stage_start[s + 1]) and the 16-byte words from its first
+// tree's first byte to the end of its last tree.  off[t] is tree t's first
+// byte in the image, or with SLOTS its first 8-byte slot, and the span is
+// rounded out to 16 bytes (layout 7's records; layout 9's trees start aligned).
+template <bool SLOTS, typename CopyT>
+struct TreeSpan {
+  struct Stage { int t0, t1; uint32_t sbase; };   // trees [t0, t1); LDS address = sbase + image byte
+  rx_cu32* off;
+  rx_cu32* sst;
+  const unsigned char* img;
+  int ns;
+  uint32_t stage_off;
+  __device__ __forceinline__ TreeSpan(const KArgs& a, const void* img_)
+      : off(reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.rx_base))),
+        sst(reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.stage_start))),
+        img(static_cast<const unsigned char*>(img_)), ns(a.n_stages),
+        stage_off((uint32_t)a.stage_off) {}
+  __device__ __forceinline__ int first() const { return 0; }
+  __device__ __forceinline__ bool more(int s) const { return s < ns; }
+  __device__ __forceinline__ int after(int s) const { return s + 1; }
+  __device__ __forceinline__ int following(int s) const { return s + 1 < ns ? s + 1 : s; }
+  __device__ __forceinline__ uint32_t lo(int s) const {
+    if constexpr (SLOTS) return (off[sst[s]] << 3) & ~15u;
+    else return off[sst[s]];
+  }
+  __device__ __forceinline__ int n16(int s) const {
+    if constexpr (SLOTS) return (int)((((off[sst[s + 1]] << 3) + 15u) & ~15u) - lo(s)) >> 4;
+    else return (int)((off[sst[s + 1]] - off[sst[s]]) >> 4);
+  }
+  __device__ __forceinline__ Stage at(int s) const {
+    return Stage{(int)sst[s], (int)sst[s + 1], stage_off - lo(s)};
+  }
+  template <int PF>
+  __device__ __forceinline__ void fetch(u32x4 (&pf)[PF], int s, int tid, int NT) const {
+    CopyT::template prefetch<PF>(pf, reinterpret_cast<const u32x4*>(img + lo(s)), n16(s), tid, NT);
+  }
+  template <int PF>
+  __device__ __forceinline__ void commit(const u32x4 (&pf)[PF], u32x4* dst, int s, int tid,
+                                         int NT) const {
+    CopyT::template commit<PF>(pf, dst, n16(s), tid, NT);
+  }
+};
+
+// The stage pipeline, for NT copying threads holding PF words each.  Two
+// entry points, so a kernel chooses whether the first fetch is in flight while
+// its tile is binned (stage_first before the binning) or not.  Then
+//   for (int c = sp.first(); sp.more(c); c = sp.after(c)) {
+//     const auto st = stage_step(sp, pf, stage, c, tid, NT);
+//     ... walk the trees of st ...
+//   }
+// where stage_step is the hand-over: barrier (the previous stage's walk is
+// over; first pass: the tile is staged), commit, barrier, the next stage's
+// loads issued.  The loop is the kernel's own and not a callback of a shared
+// loop function: with the walk as such a body the register allocation of
+// most kernels moved, by up to 30 VGPRs either way.
+template <int PF, typename Span>
+__device__ __forceinline__ void stage_first(const Span& sp, u32x4 (&pf)[PF], int tid, int NT) {
+  sp.template fetch<PF>(pf, sp.first(), tid, NT);
 }
-__device__ __forceinline__ void commit_stage(const u32x4 (&pf)[kPf], u32x4* __restrict__ dst,
-                                             int n16, int tid, int R) {
-#pragma unroll
-  for (int u = 0; u < kPf; ++u) {
-    const int i = tid + u * R;
-    if (i < n16) dst[i] = pf[u];
-  }
+template <int PF, typename Span>
+__device__ __forceinline__ typename Span::Stage stage_step(const Span& sp, u32x4 (&pf)[PF],
+                                                           unsigned char* stage, int c, int tid,
+                                                           int NT) {
+  const typename Span::Stage st = sp.at(c);
+  __syncthreads();
+  sp.template commit<PF>(pf, reinterpret_cast<u32x4*>(stage), c, tid, NT);
+  __syncthreads();
+  sp.template fetch<PF>(pf, sp.following(c), tid, NT);
+  return st;
 }
 
 // ---------------------------------------------------------------- heap kernel
@@ -431,51 +631,31 @@ __device__ __forceinline__ void heap_stage(const KArgs& a, const unsigned char* 
 template <typename XT, typename ACC, int KMAX, bool FEAT_LDS, bool ZERO>
 __global__ void __launch_bounds__(512) heap_predict_kernel(const KArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int R = blockDim.x;
-  const int tid = threadIdx.x;
-  const int64_t row0 = (int64_t)blockIdx.x * R;
-  const int64_t row = row0 + tid;
-  const bool live = row < a.n_rows;
-  const size_t feat_bytes = FEAT_LDS ? align16((size_t)a.n_features * R * sizeof(XT)) : 0;
-  volatile int* flag = reinterpret_cast<volatile int*>(smem + feat_bytes);
+  Tile t = one_lane_tile(a, (uint32_t)sizeof(XT));
+  const size_t feat_bytes = FEAT_LDS ? align16((size_t)a.n_features * t.R * sizeof(XT)) : 0;
+  t.flag = reinterpret_cast<volatile int*>(smem + feat_bytes);
   unsigned char* stage = smem + feat_bytes + 16;
   const unsigned char* xrow = reinterpret_cast<const unsigned char*>(
-      static_cast<const XT*>(a.X) + (live ? row : a.n_rows - 1) * a.row_stride);
-  const uint32_t lane_off = (uint32_t)tid * (uint32_t)sizeof(XT);
+      static_cast<const XT*>(a.X) + (t.live ? t.row : a.n_rows - 1) * a.row_stride);
   // without an LDS image the NaN path is always taken
   const bool tile_nan =
-      FEAT_LDS ? stage_features<XT>(reinterpret_cast<XT*>(smem), flag, a, row0, R, tid) : true;
-  const int T = a.n_trees;
-  const int S = a.stage_trees;
-  const int64_t stride = a.tree_stride;
+      FEAT_LDS ? stage_features<XT>(reinterpret_cast<XT*>(smem), t.flag, a, t.row0, t.R, t.tid) : true;
 
   ACC acc[KMAX];
   init_acc(acc, a);
 
-  // stage k covers trees [k*S, min(T, (k+1)*S)); the last stage re-prefetches
-  // itself so the loop body has no conditional register traffic
-  const int last0 = ((T - 1) / S) * S;
+  const FixedSpan sp(a);
   u32x4 pf[kPf];
-  prefetch_stage(pf, reinterpret_cast<const u32x4*>(a.trees),
-                 (int)(((int64_t)(T < S ? T : S) * stride) >> 4), tid, R);
-  for (int t0 = 0; t0 < T; t0 += S) {
-    const int cnt = (T - t0) < S ? (T - t0) : S;
-    __syncthreads();   // previous stage fully consumed (first pass: features staged)
-    commit_stage(pf, reinterpret_cast<u32x4*>(stage), (int)(((int64_t)cnt * stride) >> 4), tid, R);
-    __syncthreads();
-    {                  // next stage in flight while this one is walked
-      const int tn = t0 + S <= last0 ? t0 + S : last0;
-      const int cn = (T - tn) < S ? (T - tn) : S;
-      prefetch_stage(pf, reinterpret_cast<const u32x4*>(a.trees + (int64_t)tn * stride),
-                     (int)(((int64_t)cn * stride) >> 4), tid, R);
-    }
-    if (tile_nan)
-      heap_stage<XT, ACC, KMAX, FEAT_LDS, ZERO, true>(a, stage, cnt, t0, acc, lane_off, xrow, row, live);
-    else
-      heap_stage<XT, ACC, KMAX, FEAT_LDS, ZERO, false>(a, stage, cnt, t0, acc, lane_off, xrow, row, live);
+  stage_first(sp, pf, t.tid, t.R);
+  for (int c = sp.first(); sp.more(c); c = sp.after(c)) {
+    const auto st = stage_step(sp, pf, stage, c, t.tid, t.R);
+    with_flag(tile_nan, [&](auto N) {
+      heap_stage<XT, ACC, KMAX, FEAT_LDS, ZERO, decltype(N)::value>(a, stage, st.cnt, st.t0, acc, t.lane_off,
+                                                                    xrow, t.row, t.live);
+    });
   }
-  if (!live || a.kind == TI_OUTPUT_LEAF) return;
-  finish_row<ACC, KMAX>(acc, a, row);
+  if (!t.live || a.kind == TI_OUTPUT_LEAF) return;
+  finish_row<ACC, KMAX>(acc, a, t.row);
 }
 
 // ------------------------------------------------------- binned heap kernel
@@ -872,97 +1052,31 @@ __device__ __forceinline__ void bheap_stage(const KArgs& a, const unsigned char*
   }
 }
 
-template <int PF>
-__device__ __forceinline__ void prefetch_n(u32x4 (&pf)[PF], const u32x4* __restrict__ src,
-                                           int n16, int tid, int R) {
-#pragma unroll
-  for (int u = 0; u < PF; ++u) {
-    const int i = tid + u * R;
-    pf[u] = src[i < n16 ? i : n16 - 1];
-  }
-}
-template <int PF>
-__device__ __forceinline__ void commit_n(const u32x4 (&pf)[PF], u32x4* __restrict__ dst, int n16,
-                                         int tid, int R) {
-#pragma unroll
-  for (int u = 0; u < PF; ++u) {
-    const int i = tid + u * R;
-    if (i < n16) dst[i] = pf[u];
-  }
-}
-
-// Layout 9's stage copies: as prefetch_n / commit_n, but the loads address
-// the uniform base with a 32-bit byte offset (the scalar-base form of
-// global_load: an index clamp and a shift each) and the commit writes every
-// word unconditionally (a clamped lane stores the last word's own value
-// again: no compare and branch per store).  C3 5.41 -> 5.34 ms; the same
-// copies measured about 1 % slower on C2 and C4, which keep the others
-// (profiles/r2_copy_sweep.jsonl).
-template <int PF>
-__device__ __forceinline__ void prefetch_u(u32x4 (&pf)[PF], const u32x4* __restrict__ src,
-                                           int n16, int tid, int R) {
-  const unsigned char* base = reinterpret_cast<const unsigned char*>(src);
-  const uint32_t last = (uint32_t)n16 - 1u;
-#pragma unroll
-  for (int u = 0; u < PF; ++u) {
-    const uint32_t i = (uint32_t)tid + (uint32_t)(u * R);
-    pf[u] = *reinterpret_cast<const u32x4*>(base + (i < last ? i : last) * 16u);
-  }
-}
-template <int PF>
-__device__ __forceinline__ void commit_u(const u32x4 (&pf)[PF], u32x4* __restrict__ dst, int n16,
-                                         int tid, int R) {
-  const uint32_t last = (uint32_t)n16 - 1u;
-#pragma unroll
-  for (int u = 0; u < PF; ++u) {
-    const uint32_t i = (uint32_t)tid + (uint32_t)(u * R);
-    dst[i < last ? i : last] = pf[u];
-  }
-}
-
 // LDS: [bin image (bin_words * R u32)] [flag word] ... [stage area at
 // stage_off: S tree records, also the binning temp].
 template <typename XT, typename ACC, int KMAX, bool B16, int PF>
 __global__ void __launch_bounds__(512) bheap_predict_kernel(const KArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int R = blockDim.x;
-  const int tid = threadIdx.x;
-  const int64_t row0 = (int64_t)blockIdx.x * R;
-  const int64_t row = row0 + tid;
-  const bool live = row < a.n_rows;
-  volatile int* flag = reinterpret_cast<volatile int*>(smem + (size_t)a.bin_words * R * 4);
+  const Tile t = bin_tile(a, smem);
   unsigned char* stage = smem + a.stage_off;
-  const uint32_t lane_off = (uint32_t)tid * 4u;
-  const int T = a.n_trees;
-  const int S = a.stage_trees;
-  const int64_t stride = a.tree_stride;
+  const FixedSpan sp(a);
   // first stage in flight while the tile is binned
   u32x4 pf[PF];
-  prefetch_n<PF>(pf, reinterpret_cast<const u32x4*>(a.trees),
-                 (int)(((int64_t)(T < S ? T : S) * stride) >> 4), tid, R);
-  const bool tile_nan = stage_bins<XT, B16>(flag, reinterpret_cast<XT*>(stage), a, row0, R, tid);
+  stage_first(sp, pf, t.tid, t.R);
+  const bool tile_nan =
+      stage_bins<XT, B16>(t.flag, reinterpret_cast<XT*>(stage), a, t.row0, t.R, t.tid);
 
   ACC acc[KMAX];
   init_acc(acc, a);
-  const int last0 = ((T - 1) / S) * S;
-  for (int t0 = 0; t0 < T; t0 += S) {
-    const int cnt = (T - t0) < S ? (T - t0) : S;
-    __syncthreads();
-    commit_n<PF>(pf, reinterpret_cast<u32x4*>(stage), (int)(((int64_t)cnt * stride) >> 4), tid, R);
-    __syncthreads();
-    {
-      const int tn = t0 + S <= last0 ? t0 + S : last0;
-      const int cn = (T - tn) < S ? (T - tn) : S;
-      prefetch_n<PF>(pf, reinterpret_cast<const u32x4*>(a.trees + (int64_t)tn * stride),
-                     (int)(((int64_t)cn * stride) >> 4), tid, R);
-    }
-    if (tile_nan)
-      bheap_stage<ACC, KMAX, B16, true>(a, stage, cnt, t0, acc, lane_off, row, live);
-    else
-      bheap_stage<ACC, KMAX, B16, false>(a, stage, cnt, t0, acc, lane_off, row, live);
+  for (int c = sp.first(); sp.more(c); c = sp.after(c)) {
+    const auto st = stage_step(sp, pf, stage, c, t.tid, t.R);
+    with_flag(tile_nan, [&](auto N) {
+      bheap_stage<ACC, KMAX, B16, decltype(N)::value>(a, stage, st.cnt, st.t0, acc, t.lane_off, t.row,
+                                                      t.live);
+    });
   }
-  if (!live || a.kind == TI_OUTPUT_LEAF) return;
-  finish_row<ACC, KMAX>(acc, a, row);
+  if (!t.live || a.kind == TI_OUTPUT_LEAF) return;
+  finish_row<ACC, KMAX>(acc, a, t.row);
 }
 
 // ---- binned heap, fixed layout (C2: depth 8, scalar float leaves) ---------
@@ -1562,8 +1676,6 @@ __device__ __forceinline__ void rx_leaves(const KArgs& a, ACC (&acc)[KMAX], int 
   }
 }
 
-typedef const __attribute__((address_space(4))) uint32_t rx_cu32;   // scalar-loaded tables
-
 #ifndef TI_RX_ADDR2
 #define TI_RX_ADDR2 1
 #endif
@@ -1666,26 +1778,17 @@ __device__ __forceinline__ void rx_walk(const KArgs& a, ACC (&acc)[KMAX], uint32
 template <typename XT, typename ACC, int KMAX, bool ZERO, int ILP>
 __global__ void __launch_bounds__(512) rexplicit_predict_kernel(const KArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int R = blockDim.x;
-  const int tid = threadIdx.x;
-  const int64_t row0 = (int64_t)blockIdx.x * R;
-  const int64_t row = row0 + tid;
-  const bool live = row < a.n_rows;
-  volatile int* flag = reinterpret_cast<volatile int*>(smem + (size_t)a.bin_words * R * 4);
-  const bool slow = rx_stage_bins<XT, ZERO>(flag, a, row0, R, tid);
-  const uint32_t lane_off = (uint32_t)tid * 4u;
+  const Tile t = bin_tile(a, smem);
+  const bool slow = rx_stage_bins<XT, ZERO>(t.flag, a, t.row0, t.R, t.tid);
   ACC acc[KMAX];
   init_acc(acc, a);
   const bool vis = a.leaf_width == 1 && a.kind != TI_OUTPUT_LEAF;
-  if (slow) {
-    if (vis) rx_walk<ACC, KMAX, ZERO, true, true, ILP>(a, acc, lane_off, row, live);
-    else rx_walk<ACC, KMAX, ZERO, true, false, ILP>(a, acc, lane_off, row, live);
-  } else {
-    if (vis) rx_walk<ACC, KMAX, ZERO, false, true, ILP>(a, acc, lane_off, row, live);
-    else rx_walk<ACC, KMAX, ZERO, false, false, ILP>(a, acc, lane_off, row, live);
-  }
-  if (!live || a.kind == TI_OUTPUT_LEAF) return;
-  finish_row<ACC, KMAX>(acc, a, row);
+  with_flags(slow, vis, [&](auto S, auto V) {
+    rx_walk<ACC, KMAX, ZERO, decltype(S)::value, decltype(V)::value, ILP>(a, acc, t.lane_off, t.row,
+                                                                          t.live);
+  });
+  if (!t.live || a.kind == TI_OUTPUT_LEAF) return;
+  finish_row<ACC, KMAX>(acc, a, t.row);
 }
 
 // ---- staged record explicit (layout 7) -------------------------------------
@@ -1715,8 +1818,7 @@ __device__ __forceinline__ rx_u2_t lx_rec(uint32_t byte_addr) {
 // 8.4 vs 6.5 ms on C3: the branches cost the compiler's counted LDS waits.)
 template <typename ACC, int KMAX, bool ZERO, bool SLOW, bool VIS, int ILP>
 __device__ __forceinline__ void lx_stage(const KArgs& a, ACC (&acc)[KMAX], int t0, int t1,
-                                         uint32_t sbase, uint32_t lane_off, int64_t row,
-                                         bool live) {
+                                         uint32_t sbase, const Tile& t) {
   rx_cu32* rx_base = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.rx_base));
   rx_cu32* rx_nint = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.rx_nint));
   for (int j = t0; j < t1; j += ILP) {
@@ -1738,7 +1840,7 @@ __device__ __forceinline__ void lx_stage(const KArgs& a, ACC (&acc)[KMAX], int t
       for (int q = 0; q < ILP; ++q) {
         in[q] = at[q] < ni8[q];
         any |= in[q];
-        b[q] = lds_u16(rx_bin_addr(rec[q].x, in[q], lane_off));
+        b[q] = lds_u16(rx_bin_addr(rec[q].x, in[q], t.lane_off));
       }
 #pragma unroll
       for (int q = 0; q < ILP; ++q) {
@@ -1751,8 +1853,8 @@ __device__ __forceinline__ void lx_stage(const KArgs& a, ACC (&acc)[KMAX], int t
 #pragma unroll
     for (int q = 0; q < ILP; ++q)
       if (j + q < t1)
-        rx_leaves<ACC, KMAX>(a, acc, j + q, at[q] >> 3, ni8[q] >> 3, rec[q].x, rec[q].y, row, live,
-                             VIS);
+        rx_leaves<ACC, KMAX>(a, acc, j + q, at[q] >> 3, ni8[q] >> 3, rec[q].x, rec[q].y, t.row,
+                             t.live, VIS);
   }
 }
 
@@ -1760,47 +1862,24 @@ template <typename XT, typename ACC, int KMAX, bool ZERO, int ILP>
 __global__ void __launch_bounds__(512) lexplicit_predict_kernel(const KArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int PF = 8;   // = kLxPf (host): a stage is at most PF x 16 B x R
-  const int R = blockDim.x;
-  const int tid = threadIdx.x;
-  const int64_t row0 = (int64_t)blockIdx.x * R;
-  const int64_t row = row0 + tid;
-  const bool live = row < a.n_rows;
-  volatile int* flag = reinterpret_cast<volatile int*>(smem + (size_t)a.bin_words * R * 4);
-  u32x4* stage = reinterpret_cast<u32x4*>(smem + a.stage_off);
-  const uint32_t lane_off = (uint32_t)tid * 4u;
-  rx_cu32* rx_base = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.rx_base));
-  rx_cu32* sst = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.stage_start));
-  const unsigned char* recs = reinterpret_cast<const unsigned char*>(a.rx_recs);
-  const int NS = a.n_stages;
-  // a stage's span: the 16-byte words from its first tree's slot 0 to the
-  // end of its last tree
-  auto lo_of = [&](int s) { return (rx_base[sst[s]] << 3) & ~15u; };
-  auto n16_of = [&](int s) { return (int)((((rx_base[sst[s + 1]] << 3) + 15u) & ~15u) - lo_of(s)) >> 4; };
+  const Tile t = bin_tile(a, smem);
+  unsigned char* stage = smem + a.stage_off;
+  const TreeSpan<true, CopyN> sp(a, a.rx_recs);
   u32x4 pf[PF];
-  prefetch_n<PF>(pf, reinterpret_cast<const u32x4*>(recs + lo_of(0)), n16_of(0), tid, R);
-  const bool slow = rx_stage_bins<XT, ZERO>(flag, a, row0, R, tid, stage);
+  stage_first(sp, pf, t.tid, t.R);
+  const bool slow = rx_stage_bins<XT, ZERO>(t.flag, a, t.row0, t.R, t.tid, stage);
   const bool vis = a.leaf_width == 1 && a.kind != TI_OUTPUT_LEAF;
   ACC acc[KMAX];
   init_acc(acc, a);
-  for (int s = 0; s < NS; ++s) {
-    const int t0 = (int)sst[s], t1 = (int)sst[s + 1];
-    const uint32_t lo = lo_of(s);
-    __syncthreads();   // the previous stage's walk is over
-    commit_n<PF>(pf, stage, n16_of(s), tid, R);
-    __syncthreads();
-    const int sn = s + 1 < NS ? s + 1 : s;
-    prefetch_n<PF>(pf, reinterpret_cast<const u32x4*>(recs + lo_of(sn)), n16_of(sn), tid, R);
-    const uint32_t sbase = (uint32_t)a.stage_off - lo;   // LDS address = sbase + record byte
-    if (slow) {
-      if (vis) lx_stage<ACC, KMAX, ZERO, true, true, ILP>(a, acc, t0, t1, sbase, lane_off, row, live);
-      else lx_stage<ACC, KMAX, ZERO, true, false, ILP>(a, acc, t0, t1, sbase, lane_off, row, live);
-    } else {
-      if (vis) lx_stage<ACC, KMAX, ZERO, false, true, ILP>(a, acc, t0, t1, sbase, lane_off, row, live);
-      else lx_stage<ACC, KMAX, ZERO, false, false, ILP>(a, acc, t0, t1, sbase, lane_off, row, live);
-    }
+  for (int c = sp.first(); sp.more(c); c = sp.after(c)) {
+    const auto st = stage_step(sp, pf, stage, c, t.tid, t.R);
+    with_flags(slow, vis, [&](auto S, auto V) {
+      lx_stage<ACC, KMAX, ZERO, decltype(S)::value, decltype(V)::value, ILP>(a, acc, st.t0, st.t1,
+                                                                             st.sbase, t);
+    });
   }
-  if (!live || a.kind == TI_OUTPUT_LEAF) return;
-  finish_row<ACC, KMAX>(acc, a, row);
+  if (!t.live || a.kind == TI_OUTPUT_LEAF) return;
+  finish_row<ACC, KMAX>(acc, a, t.row);
 }
 
 // ---- heap top + record bottom (layout 8) -----------------------------------
@@ -1826,48 +1905,97 @@ __device__ __forceinline__ bool rx_right_slow(uint32_t x, uint32_t b) {
   return right;
 }
 
+// The heap top of a group of ILP trees (layout 8, and layout 9's u8 bottom):
+// from each tree's root (one broadcast read) down D0 levels of {bin read +
+// read of the two children}, one LDS round trip a level; the last level
+// selects the entry where the bottom starts, left in nd.  Bins says how a top
+// word names its bin and its rank:
+//   bin(nd, lane_off)    the lane's bin of the node's feature
+//   right_slow<ZERO>     the decision on tiles with a NaN or an exact zero
+//   kByteRank            the rank is byte 2 of the word (else its high half)
+// and Pair where a tree's top is: `at_t` addresses it, root(at) reads the root
+// word and pair(at, i) node i's children.  (tx_stage and t16_stage walk the
+// same top in a copy of their own: see there.)
+struct TopU16Bins {   // layout 6's x words, u16 bins
+  static constexpr bool kByteRank = false;
+  static __device__ __forceinline__ uint32_t bin(uint32_t nd, uint32_t lane_off) {
+    return lds_u16((nd & kRxOffMask) | lane_off);
+  }
+  template <bool ZERO> static __device__ __forceinline__ bool right_slow(uint32_t nd, uint32_t b) {
+    return rx_right_slow<ZERO>(nd, b);
+  }
+};
+struct PairPtr {   // a pointer to the tree's top
+  using at_t = const uint32_t*;
+  using pair_t = uint2;
+  static __device__ __forceinline__ uint32_t root(at_t tp) { return tp[1]; }
+  static __device__ __forceinline__ pair_t pair(at_t tp, uint32_t i) {
+    return *reinterpret_cast<const uint2*>(tp + 2u * i);
+  }
+};
+struct PairLds {   // the top's LDS byte address
+  using at_t = uint32_t;
+  using pair_t = rx_u2_t;
+  static __device__ __forceinline__ uint32_t root(at_t base) { return lds_u32(base + 4u); }
+  static __device__ __forceinline__ pair_t pair(at_t base, uint32_t i) { return lx_rec(base + 8u * i); }
+};
+
+template <int ILP, bool SLOW, bool ZERO, typename Bins, typename Pair>
+__device__ __forceinline__ void heap_top(const typename Pair::at_t (&at)[ILP], int D0,
+                                         uint32_t lane_off, uint32_t (&nd)[ILP]) {
+  uint32_t idx[ILP];
+#pragma unroll
+  for (int q = 0; q < ILP; ++q) {
+    idx[q] = 1u;
+    nd[q] = Pair::root(at[q]);
+  }
+  for (int l = 0; l < D0; ++l) {
+    uint32_t b[ILP];
+    typename Pair::pair_t pr[ILP];
+#pragma unroll
+    for (int q = 0; q < ILP; ++q) {
+      b[q] = Bins::bin(nd[q], lane_off);
+      pr[q] = Pair::pair(at[q], idx[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < ILP; ++q) {
+      if constexpr (SLOW) {
+        const bool right = Bins::template right_slow<ZERO>(nd[q], b[q]);
+        idx[q] = idx[q] + idx[q] + (uint32_t)right;
+        nd[q] = right ? pr[q].y : pr[q].x;
+      } else if constexpr (Bins::kByteRank) {
+        asm("v_cmp_lt_u32_sdwa vcc, %0, %2 src0_sel:BYTE_2 src1_sel:DWORD\n\t"
+            "v_cndmask_b32 %0, %3, %4, vcc\n\t"
+            "v_addc_co_u32 %1, vcc, %1, %1, vcc"
+            : "+v"(nd[q]), "+v"(idx[q]) : "v"(b[q]), "v"(pr[q].x), "v"(pr[q].y)
+            : "vcc");
+      } else {
+        // right = rank < bin, the child word from the pair, idx = 2 idx + right
+        asm("v_cmp_lt_u32_sdwa vcc, %0, %2 src0_sel:WORD_1 src1_sel:DWORD\n\t"
+            "v_cndmask_b32 %0, %3, %4, vcc\n\t"
+            "v_addc_co_u32 %1, vcc, %1, %1, vcc"
+            : "+v"(nd[q]), "+v"(idx[q]) : "v"(b[q]), "v"(pr[q].x), "v"(pr[q].y)
+            : "vcc");
+      }
+    }
+  }
+}
+
 template <typename ACC, int KMAX, bool ZERO, bool SLOW, bool VIS, int ILP>
 __device__ __forceinline__ void hx_stage(const KArgs& a, ACC (&acc)[KMAX], const rx_rsrc_t rsrc,
-                                         const unsigned char* stage, int t0, int cnt,
-                                         uint32_t lane_off, int64_t row, bool live) {
+                                         const unsigned char* stage, int t0, int cnt, const Tile& t) {
   rx_cu32* rx_base = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.rx_base));
   rx_cu32* rx_nint = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.rx_nint));
-  const int D0 = a.depth;
   const int64_t stride = a.tree_stride;
   for (int j = 0; j < cnt; j += ILP) {
     const uint32_t* tp[ILP];
-    uint32_t idx[ILP], nd[ILP];
+    uint32_t nd[ILP];
 #pragma unroll
     for (int q = 0; q < ILP; ++q) {
       const int tq = (j + q) < cnt ? (j + q) : (cnt - 1);
       tp[q] = reinterpret_cast<const uint32_t*>(stage + (int64_t)tq * stride);
-      idx[q] = 1u;
-      nd[q] = tp[q][1];   // the root: one broadcast read
     }
-    for (int l = 0; l < D0; ++l) {   // the last level selects the bottom slot
-      uint32_t b[ILP];
-      uint2 pr[ILP];
-#pragma unroll
-      for (int q = 0; q < ILP; ++q) {
-        b[q] = lds_u16((nd[q] & kRxOffMask) | lane_off);
-        pr[q] = *reinterpret_cast<const uint2*>(tp[q] + 2u * idx[q]);
-      }
-#pragma unroll
-      for (int q = 0; q < ILP; ++q) {
-        if (!SLOW) {
-          // right = rank < bin, the child word from the pair, idx = 2 idx + right
-          asm("v_cmp_lt_u32_sdwa vcc, %0, %2 src0_sel:WORD_1 src1_sel:DWORD\n\t"
-              "v_cndmask_b32 %0, %3, %4, vcc\n\t"
-              "v_addc_co_u32 %1, vcc, %1, %1, vcc"
-              : "+v"(nd[q]), "+v"(idx[q]) : "v"(b[q]), "v"(pr[q].x), "v"(pr[q].y)
-              : "vcc");
-        } else {
-          const bool right = rx_right_slow<ZERO>(nd[q], b[q]);
-          idx[q] = idx[q] + idx[q] + (uint32_t)right;
-          nd[q] = right ? pr[q].y : pr[q].x;
-        }
-      }
-    }
+    heap_top<ILP, SLOW, ZERO, TopU16Bins, PairPtr>(tp, a.depth, t.lane_off, nd);
     uint32_t sb[ILP], ni[ILP], slot[ILP];
     rx_u2_t rec[ILP];
 #pragma unroll
@@ -1879,11 +2007,11 @@ __device__ __forceinline__ void hx_stage(const KArgs& a, ACC (&acc)[KMAX], const
     }
 #pragma unroll
     for (int q = 0; q < ILP; ++q) rec[q] = rx_struct_load(rsrc, slot[q], 0u, sb[q], 0);
-    rx_descend<ZERO, SLOW, ILP>(rsrc, sb, ni, slot, rec, lane_off);
+    rx_descend<ZERO, SLOW, ILP>(rsrc, sb, ni, slot, rec, t.lane_off);
 #pragma unroll
     for (int q = 0; q < ILP; ++q)
       if (j + q < cnt)
-        rx_leaves<ACC, KMAX>(a, acc, t0 + j + q, slot[q], ni[q], rec[q].x, rec[q].y, row, live,
+        rx_leaves<ACC, KMAX>(a, acc, t0 + j + q, slot[q], ni[q], rec[q].x, rec[q].y, t.row, t.live,
                              VIS);
   }
 }
@@ -1893,47 +2021,25 @@ template <typename XT, typename ACC, int KMAX, bool ZERO, int ILP>
 __global__ void __launch_bounds__(512) hexplicit_predict_kernel(const KArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int PF = 8;   // = kHxPf (host): a stage is at most PF x 16 B x R
-  const int R = blockDim.x;
-  const int tid = threadIdx.x;
-  const int64_t row0 = (int64_t)blockIdx.x * R;
-  const int64_t row = row0 + tid;
-  const bool live = row < a.n_rows;
-  volatile int* flag = reinterpret_cast<volatile int*>(smem + (size_t)a.bin_words * R * 4);
+  const Tile t = bin_tile(a, smem);
   unsigned char* stage = smem + a.stage_off;
-  const uint32_t lane_off = (uint32_t)tid * 4u;
-  const int T = a.n_trees;
-  const int S = a.stage_trees;
-  const int64_t stride = a.tree_stride;
+  const FixedSpan sp(a);
   const rx_rsrc_t rsrc = rx_make_rsrc(a.rx_recs, a.rx_slots);
   u32x4 pf[PF];
-  prefetch_n<PF>(pf, reinterpret_cast<const u32x4*>(a.trees),
-                 (int)(((int64_t)(T < S ? T : S) * stride) >> 4), tid, R);
-  const bool slow = rx_stage_bins<XT, ZERO, true>(flag, a, row0, R, tid, stage);
+  stage_first(sp, pf, t.tid, t.R);
+  const bool slow = rx_stage_bins<XT, ZERO, true>(t.flag, a, t.row0, t.R, t.tid, stage);
   const bool vis = a.leaf_width == 1 && a.kind != TI_OUTPUT_LEAF;
   ACC acc[KMAX];
   init_acc(acc, a);
-  const int last0 = ((T - 1) / S) * S;
-  for (int t0 = 0; t0 < T; t0 += S) {
-    const int cnt = (T - t0) < S ? (T - t0) : S;
-    __syncthreads();   // the previous stage's walk is over
-    commit_n<PF>(pf, reinterpret_cast<u32x4*>(stage), (int)(((int64_t)cnt * stride) >> 4), tid, R);
-    __syncthreads();
-    {
-      const int tn = t0 + S <= last0 ? t0 + S : last0;
-      const int cn = (T - tn) < S ? (T - tn) : S;
-      prefetch_n<PF>(pf, reinterpret_cast<const u32x4*>(a.trees + (int64_t)tn * stride),
-                     (int)(((int64_t)cn * stride) >> 4), tid, R);
-    }
-    if (slow) {
-      if (vis) hx_stage<ACC, KMAX, ZERO, true, true, ILP>(a, acc, rsrc, stage, t0, cnt, lane_off, row, live);
-      else hx_stage<ACC, KMAX, ZERO, true, false, ILP>(a, acc, rsrc, stage, t0, cnt, lane_off, row, live);
-    } else {
-      if (vis) hx_stage<ACC, KMAX, ZERO, false, true, ILP>(a, acc, rsrc, stage, t0, cnt, lane_off, row, live);
-      else hx_stage<ACC, KMAX, ZERO, false, false, ILP>(a, acc, rsrc, stage, t0, cnt, lane_off, row, live);
-    }
+  for (int c = sp.first(); sp.more(c); c = sp.after(c)) {
+    const auto st = stage_step(sp, pf, stage, c, t.tid, t.R);
+    with_flags(slow, vis, [&](auto S, auto V) {
+      hx_stage<ACC, KMAX, ZERO, decltype(S)::value, decltype(V)::value, ILP>(a, acc, rsrc, stage, st.t0,
+                                                                              st.cnt, t);
+    });
   }
-  if (!live || a.kind == TI_OUTPUT_LEAF) return;
-  finish_row<ACC, KMAX>(acc, a, row);
+  if (!t.live || a.kind == TI_OUTPUT_LEAF) return;
+  finish_row<ACC, KMAX>(acc, a, t.row);
 }
 
 // ---- heap top + staged bottom (layout 9) -----------------------------------
@@ -1948,14 +2054,17 @@ __global__ void __launch_bounds__(512) hexplicit_predict_kernel(const KArgs a) {
 // group runs for its deepest path), then the bottom in layout 7's lockstep.
 // KArgs: trees = image, depth = D0, rx_base = byte offset of each tree in the
 // image [T+1], rx_nint = internal nodes of each bottom [T].
+// tx_stage keeps its own copy of the heap top (heap_top's walk) and of the
+// lockstep bottom (lx_stage's loop, with B8): built from shared functions,
+// nine of its 16-group instantiations at 7 or 8 trees a lane moved by one or
+// two VGPRs or two SGPRs (scripts/kernel_resources.py; the arrays passed by
+// reference are split into registers differently).
 template <typename ACC, int KMAX, bool ZERO, bool SLOW, bool VIS, int ILP, bool B8>
 __device__ __forceinline__ void tx_stage(const KArgs& a, ACC (&acc)[KMAX], int t0, int t1,
-                                         uint32_t sbase, uint32_t lane_off, int64_t row,
-                                         bool live) {
+                                         uint32_t sbase, const Tile& t) {
   rx_cu32* tx_off = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.rx_base));
   rx_cu32* tx_nint = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.rx_nint));
-  const int D0 = a.depth;
-  const uint32_t topb = 8u << D0;   // 2^(D0+1) u32
+  const uint32_t topb = 8u << a.depth;   // 2^(D0+1) u32
   for (int j = t0; j < t1; j += ILP) {
     uint32_t base[ILP], ni8[ILP], at[ILP], idx[ILP], nd[ILP];
 #pragma unroll
@@ -1964,15 +2073,14 @@ __device__ __forceinline__ void tx_stage(const KArgs& a, ACC (&acc)[KMAX], int t
       base[q] = sbase + tx_off[tq];
       ni8[q] = tx_nint[tq] << 3;
       idx[q] = 1u;
-      nd[q] = *reinterpret_cast<const __attribute__((address_space(3))) uint32_t*>(
-          static_cast<uintptr_t>(base[q] + 4u));   // the root: one broadcast read
+      nd[q] = lds_u32(base[q] + 4u);   // the root: one broadcast read
     }
-    for (int l = 0; l < D0; ++l) {   // the last level selects the bottom entry
+    for (int l = 0; l < a.depth; ++l) {   // the last level selects the bottom entry
       uint32_t b[ILP];
       rx_u2_t pr[ILP];
 #pragma unroll
       for (int q = 0; q < ILP; ++q) {
-        b[q] = lds_rxbin<B8>((nd[q] & RxBins<B8>::kOffMask) | lane_off);
+        b[q] = lds_rxbin<B8>((nd[q] & RxBins<B8>::kOffMask) | t.lane_off);
         pr[q] = lx_rec(base[q] + 8u * idx[q]);
       }
 #pragma unroll
@@ -2005,7 +2113,7 @@ __device__ __forceinline__ void tx_stage(const KArgs& a, ACC (&acc)[KMAX], int t
       for (int q = 0; q < ILP; ++q) {
         in[q] = at[q] < ni8[q];
         any |= in[q];
-        b[q] = lds_rxbin<B8>(rx_bin_addr<B8>(rec[q].x, in[q], lane_off));
+        b[q] = lds_rxbin<B8>(rx_bin_addr<B8>(rec[q].x, in[q], t.lane_off));
       }
 #pragma unroll
       for (int q = 0; q < ILP; ++q) {
@@ -2018,7 +2126,7 @@ __device__ __forceinline__ void tx_stage(const KArgs& a, ACC (&acc)[KMAX], int t
 #pragma unroll
     for (int q = 0; q < ILP; ++q)
       if (j + q < t1)
-        rx_leaves<ACC, KMAX>(a, acc, j + q, at[q] >> 3, ni8[q] >> 3, rec[q].x, rec[q].y, row, live,
+        rx_leaves<ACC, KMAX>(a, acc, j + q, at[q] >> 3, ni8[q] >> 3, rec[q].x, rec[q].y, t.row, t.live,
                              VIS);
   }
 }
@@ -2027,45 +2135,24 @@ template <typename XT, typename ACC, int KMAX, bool ZERO, int ILP, bool B8 = fal
 __global__ void __launch_bounds__(512) texplicit_predict_kernel(const KArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int PF = 8;   // = kLxPf (host): a stage is at most PF x 16 B x R
-  const int R = blockDim.x;
-  const int tid = threadIdx.x;
-  const int64_t row0 = (int64_t)blockIdx.x * R;
-  const int64_t row = row0 + tid;
-  const bool live = row < a.n_rows;
-  volatile int* flag = reinterpret_cast<volatile int*>(smem + (size_t)a.bin_words * R * 4);
-  u32x4* stage = reinterpret_cast<u32x4*>(smem + a.stage_off);
-  const uint32_t lane_off = (uint32_t)tid * 4u;
-  rx_cu32* tx_off = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.rx_base));
-  rx_cu32* sst = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.stage_start));
-  const unsigned char* img = a.trees;
-  const int NS = a.n_stages;
-  auto lo_of = [&](int s) { return tx_off[sst[s]]; };   // trees start 16-byte aligned
-  auto n16_of = [&](int s) { return (int)((tx_off[sst[s + 1]] - tx_off[sst[s]]) >> 4); };
+  const Tile t = bin_tile(a, smem);
+  unsigned char* stage = smem + a.stage_off;
+  const TreeSpan<false, CopyU> sp(a, a.trees);
   u32x4 pf[PF];
-  prefetch_u<PF>(pf, reinterpret_cast<const u32x4*>(img + lo_of(0)), n16_of(0), tid, R);
-  const bool slow = rx_stage_bins<XT, ZERO, false, B8>(flag, a, row0, R, tid, stage);
+  stage_first(sp, pf, t.tid, t.R);
+  const bool slow = rx_stage_bins<XT, ZERO, false, B8>(t.flag, a, t.row0, t.R, t.tid, stage);
   const bool vis = a.leaf_width == 1 && a.kind != TI_OUTPUT_LEAF;
   ACC acc[KMAX];
   init_acc(acc, a);
-  for (int s = 0; s < NS; ++s) {
-    const int t0 = (int)sst[s], t1 = (int)sst[s + 1];
-    const uint32_t lo = lo_of(s);
-    __syncthreads();   // the previous stage's walk is over
-    commit_u<PF>(pf, stage, n16_of(s), tid, R);
-    __syncthreads();
-    const int sn = s + 1 < NS ? s + 1 : s;
-    prefetch_u<PF>(pf, reinterpret_cast<const u32x4*>(img + lo_of(sn)), n16_of(sn), tid, R);
-    const uint32_t sbase = (uint32_t)a.stage_off - lo;   // LDS address = sbase + image byte
-    if (slow) {
-      if (vis) tx_stage<ACC, KMAX, ZERO, true, true, ILP, B8>(a, acc, t0, t1, sbase, lane_off, row, live);
-      else tx_stage<ACC, KMAX, ZERO, true, false, ILP, B8>(a, acc, t0, t1, sbase, lane_off, row, live);
-    } else {
-      if (vis) tx_stage<ACC, KMAX, ZERO, false, true, ILP, B8>(a, acc, t0, t1, sbase, lane_off, row, live);
-      else tx_stage<ACC, KMAX, ZERO, false, false, ILP, B8>(a, acc, t0, t1, sbase, lane_off, row, live);
-    }
+  for (int c = sp.first(); sp.more(c); c = sp.after(c)) {
+    const auto st = stage_step(sp, pf, stage, c, t.tid, t.R);
+    with_flags(slow, vis, [&](auto S, auto V) {
+      tx_stage<ACC, KMAX, ZERO, decltype(S)::value, decltype(V)::value, ILP, B8>(a, acc, st.t0, st.t1,
+                                                                                  st.sbase, t);
+    });
   }
-  if (!live || a.kind == TI_OUTPUT_LEAF) return;
-  finish_row<ACC, KMAX>(acc, a, row);
+  if (!t.live || a.kind == TI_OUTPUT_LEAF) return;
+  finish_row<ACC, KMAX>(acc, a, t.row);
 }
 
 
@@ -2097,191 +2184,13 @@ __device__ __forceinline__ void t8_flush(const KArgs& a, ACC (&acc)[KMAX], const
     if (pend_t[q] >= 0) add_leaf<ACC, KMAX>(acc, &pend[q], 0, 1, a.tree_group[pend_t[q]]);
 }
 
-template <typename ACC, int KMAX, bool ZERO, bool SLOW, bool VIS, int ILP>
-__device__ __forceinline__ void t8_stage(const KArgs& a, ACC (&acc)[KMAX], int t0, int t1,
-                                         uint32_t sbase, uint32_t lane_off, int64_t row, bool live,
-                                         ACC (&pend)[ILP], int (&pend_t)[ILP]) {
-  using W = RxBins<true>;
-  rx_cu32* tx_off = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.rx_base));
-  rx_cu32* tx_pos = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.tx_pos));
-  const int D0 = a.depth;
-  const uint32_t topb = 8u << D0;   // 2^(D0+1) u32
-  for (int j = t0; j < t1; j += ILP) {
-    uint32_t base[ILP], idx[ILP], nd[ILP];
-#pragma unroll
-    for (int q = 0; q < ILP; ++q) {
-      const int tq = (j + q) < t1 ? (j + q) : (t1 - 1);
-      base[q] = sbase + tx_off[tq];
-      idx[q] = 1u;
-      nd[q] = *reinterpret_cast<const __attribute__((address_space(3))) uint32_t*>(
-          static_cast<uintptr_t>(base[q] + 4u));   // the root: one broadcast read
-    }
-    for (int l = 0; l < D0; ++l) {   // the last level selects the bottom entry
-      uint32_t b[ILP];
-      rx_u2_t pr[ILP];
-#pragma unroll
-      for (int q = 0; q < ILP; ++q) {
-        b[q] = lds_u8((nd[q] & W::kNodeMask) | lane_off);
-        pr[q] = lx_rec(base[q] + 8u * idx[q]);
-      }
-#pragma unroll
-      for (int q = 0; q < ILP; ++q) {
-        if (!SLOW) {
-          asm("v_cmp_lt_u32_sdwa vcc, %0, %2 src0_sel:BYTE_2 src1_sel:DWORD\n\t"
-              "v_cndmask_b32 %0, %3, %4, vcc\n\t"
-              "v_addc_co_u32 %1, vcc, %1, %1, vcc"
-              : "+v"(nd[q]), "+v"(idx[q]) : "v"(b[q]), "v"(pr[q].x), "v"(pr[q].y)
-              : "vcc");
-        } else {
-          const bool right = t8_right_slow<ZERO>(nd[q], b[q]);
-          idx[q] = idx[q] + idx[q] + (uint32_t)right;
-          nd[q] = right ? pr[q].y : pr[q].x;
-        }
-      }
-    }
-    uint32_t x[ILP];
-#pragma unroll
-    for (int q = 0; q < ILP; ++q) {
-      base[q] += topb;   // the bottom: u32 words by position
-      x[q] = *reinterpret_cast<const __attribute__((address_space(3))) uint32_t*>(
-          static_cast<uintptr_t>(base[q] + 4u * nd[q]));
-    }
-    for (;;) {
-      uint32_t all = x[0];
-#pragma unroll
-      for (int q = 1; q < ILP; ++q) all &= x[q];
-      if (__ballot((all & W::kLeaf) == 0u) == 0) break;   // every lane of every tree at a leaf
-      uint32_t b[ILP];
-      rx_u2_t pr[ILP];
-#pragma unroll
-      for (int q = 0; q < ILP; ++q) {
-        b[q] = lds_u8((x[q] & W::kNodeMask) | lane_off);
-        pr[q] = lx_rec(base[q] + ((x[q] >> 24) << 3));
-      }
-#pragma unroll
-      for (int q = 0; q < ILP; ++q) {
-        if (!SLOW) {
-          asm("v_cmp_lt_u32_sdwa vcc, %0, %1 src0_sel:BYTE_2 src1_sel:DWORD\n\t"
-              "v_cndmask_b32 %0, %2, %3, vcc"
-              : "+v"(x[q]) : "v"(b[q]), "v"(pr[q].x), "v"(pr[q].y) : "vcc");
-        } else {
-          x[q] = t8_right_slow<ZERO>(x[q], b[q]) ? pr[q].y : pr[q].x;
-        }
-      }
-    }
-    uint32_t li[ILP];   // the leaf's index in the position tables
-#pragma unroll
-    for (int q = 0; q < ILP; ++q) {
-      const int tq = (j + q) < t1 ? (j + q) : (t1 - 1);
-      li[q] = tx_pos[tq] + ((x[q] >> 23) & ~1u) + (((x[q] >> 16) & 0xFFu) == 0u ? 1u : 0u);
-    }
-    if (VIS) {
-      t8_flush<ACC, KMAX, ILP>(a, acc, pend, pend_t);   // the previous group's leaves
-#pragma unroll
-      for (int q = 0; q < ILP; ++q) {
-        pend[q] = static_cast<const ACC*>(a.tx_vals)[li[q]];
-        pend_t[q] = (j + q) < t1 ? (j + q) : -1;
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < ILP; ++q) {
-        const int t = j + q;
-        if (t < t1) {
-          const int64_t lf = a.leaf_base[t] + (int64_t)a.tx_ord[li[q]];
-          if (a.kind == TI_OUTPUT_LEAF) {
-            if (live) static_cast<int32_t*>(a.out)[row * a.n_trees + t] = a.exp_leaf_ids[lf];
-          } else {
-            add_leaf<ACC, KMAX>(acc, static_cast<const ACC*>(a.leaves) + lf * a.leaf_width, 0,
-                                a.leaf_width, a.tree_group[t]);
-          }
-        }
-      }
-    }
-  }
-}
-
-template <typename XT, typename ACC, int KMAX, bool ZERO, int ILP>
-__global__ void __launch_bounds__(512) t8explicit_predict_kernel(const KArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int PF = 8;   // = kLxPf (host): a stage is at most PF x 16 B x R
-  const int R = blockDim.x;
-  const int tid = threadIdx.x;
-  const int64_t row0 = (int64_t)blockIdx.x * R;
-  const int64_t row = row0 + tid;
-  const bool live = row < a.n_rows;
-  volatile int* flag = reinterpret_cast<volatile int*>(smem + (size_t)a.bin_words * R * 4);
-  u32x4* stage = reinterpret_cast<u32x4*>(smem + a.stage_off);
-  const uint32_t lane_off = (uint32_t)tid * 4u;
-  rx_cu32* tx_off = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.rx_base));
-  rx_cu32* sst = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.stage_start));
-  const unsigned char* img = a.trees;
-  const int NS = a.n_stages;
-  auto lo_of = [&](int s) { return tx_off[sst[s]]; };   // trees start 16-byte aligned
-  auto n16_of = [&](int s) { return (int)((tx_off[sst[s + 1]] - tx_off[sst[s]]) >> 4); };
-  u32x4 pf[PF];
-  prefetch_u<PF>(pf, reinterpret_cast<const u32x4*>(img + lo_of(0)), n16_of(0), tid, R);
-  const bool slow = rx_stage_bins<XT, ZERO, false, true>(flag, a, row0, R, tid, stage);
-  const bool vis = a.leaf_width == 1 && a.kind != TI_OUTPUT_LEAF;
-  ACC acc[KMAX];
-  init_acc(acc, a);
-  ACC pend[ILP];   // the previous group's leaf values (t8_stage)
-  int pend_t[ILP];
+template <typename ACC, int ILP>
+__device__ __forceinline__ void pend_init(ACC (&pend)[ILP], int (&pend_t)[ILP]) {
 #pragma unroll
   for (int q = 0; q < ILP; ++q) {
     pend[q] = ACC(0);
     pend_t[q] = -1;
   }
-  for (int s = 0; s < NS; ++s) {
-    const int t0 = (int)sst[s], t1 = (int)sst[s + 1];
-    const uint32_t lo = lo_of(s);
-    __syncthreads();   // the previous stage's walk is over
-    commit_u<PF>(pf, stage, n16_of(s), tid, R);
-    __syncthreads();
-    const int sn = s + 1 < NS ? s + 1 : s;
-    prefetch_u<PF>(pf, reinterpret_cast<const u32x4*>(img + lo_of(sn)), n16_of(sn), tid, R);
-    const uint32_t sbase = (uint32_t)a.stage_off - lo;   // LDS address = sbase + image byte
-    if (slow) {
-      if (vis) t8_stage<ACC, KMAX, ZERO, true, true, ILP>(a, acc, t0, t1, sbase, lane_off, row, live, pend, pend_t);
-      else t8_stage<ACC, KMAX, ZERO, true, false, ILP>(a, acc, t0, t1, sbase, lane_off, row, live, pend, pend_t);
-    } else {
-      if (vis) t8_stage<ACC, KMAX, ZERO, false, true, ILP>(a, acc, t0, t1, sbase, lane_off, row, live, pend, pend_t);
-      else t8_stage<ACC, KMAX, ZERO, false, false, ILP>(a, acc, t0, t1, sbase, lane_off, row, live, pend, pend_t);
-    }
-  }
-  if (vis) t8_flush<ACC, KMAX, ILP>(a, acc, pend, pend_t);
-  if (!live || a.kind == TI_OUTPUT_LEAF) return;
-  finish_row<ACC, KMAX>(acc, a, row);
-}
-
-// ---- layout 9 with the compact u16 bottom (plan_tx16) -----------------------
-// The u8 compact bottom's step for u16 bins (C3: ~2,500 thresholds a feature).
-// A bottom node is one u32: rank in the high half (the compare reads WORD_1,
-// as the record walk's), the bin's byte offset in the low half with the lane
-// part cleared (bit 0 NaN-left, bit 1 the half-word, the word index above the
-// lane bits), and the children's pair index k' in bits 2-9 -- inside the lane
-// part, which the bin address masks off (a.bin_mask).  Children sit side by
-// side at positions 2k', 2k'+1, so a step is one LDS round trip (the u16 bin
-// and the 8-byte pair) and 5 VALU, against the record bottom's two round trips
-// and 7 VALU.  A leaf loops on itself (rank 0xFFFF at even positions: never
-// right, NaN-left; rank 0 at odd ones: always right, since every real bin is
-// >= 1 and a NaN takes the NaN-left bit) with bin offset 0, so a finished
-// lane reads its own column of word 0 (conflict-free, a real bin: a read of
-// anything else could return 0 and send an odd leaf to its sibling).  No
-// internal node has rank 0 or 0xFFFF (plan_tx16 checks), so the group's loop
-// ends when every tree's rank is one of those: (x + 0x10000) < 0x20000.  LightGBM's
-// zero flip has no bit left in the word: zero-missing forests keep one flag
-// bit per position in a 64-byte table between the top and the bottom, read by
-// the slow step (tiles holding an exact 0 or a NaN), which tracks the node's
-// position.  Leaf values come from the position tables as in t8_stage.
-constexpr uint32_t kT16ZfBytes = 64;   // zero-flip bits of <= 512 positions
-
-template <bool ZERO>
-__device__ __forceinline__ bool t16_right_slow(uint32_t x, uint32_t b, bool zf) {
-  constexpr uint32_t kNan = RxBins<false>::template nan_code<ZERO>();
-  bool right = (x >> 16) < b;
-  if (ZERO) right = right != (((b & 1u) != 0u) && zf);
-  if (b == kNan) right = (x & 1u) == 0u;
-  return right;
 }
 
 // The two-lanes-a-row walk (t16split_predict_kernel): a lane's partner
@@ -2322,20 +2231,179 @@ __device__ __forceinline__ void t16_flush_split(const KArgs& a, ACC (&acc)[KMAX]
   t8_flush<ACC, KMAX, ILP>(a, acc, pp, pt);
 }
 
-template <typename ACC, int KMAX, bool ZERO, bool SLOW, bool VIS, int ILP, bool SPLIT = false>
-__device__ __forceinline__ void t16_stage(const KArgs& a, ACC (&acc)[KMAX], int t0, int t1,
-                                          uint32_t sbase, uint32_t lane_off, int64_t row,
-                                          bool live, ACC (&pend)[ILP], int (&pend_t)[ILP],
-                                          int half = 0) {
+// The leaves of a group of the compact bottoms, found at li[] in the forest's
+// position tables: values (VIS) are loaded now and added when the next group
+// ends; ordinals give the leaf id or the vector leaf at once.  SPLIT: the
+// group's two halves sit in partner lanes (t16_flush_split).
+template <typename ACC, int KMAX, bool VIS, int ILP, bool SPLIT>
+__device__ __forceinline__ void pos_leaves(const KArgs& a, ACC (&acc)[KMAX], int j, int t1,
+                                           const uint32_t (&li)[ILP], const Tile& t,
+                                           ACC (&pend)[ILP], int (&pend_t)[ILP]) {
+  if (VIS) {
+    // the previous group's leaves
+    if (SPLIT) t16_flush_split<ACC, KMAX, ILP>(a, acc, pend, pend_t);
+    else t8_flush<ACC, KMAX, ILP>(a, acc, pend, pend_t);
+#pragma unroll
+    for (int q = 0; q < ILP; ++q) {
+      pend[q] = static_cast<const ACC*>(a.tx_vals)[li[q]];
+      pend_t[q] = (j + q) < t1 ? (j + q) : -1;
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < ILP; ++q) {
+      const int tr = j + q;
+      if (tr < t1) {
+        const int64_t lf = a.leaf_base[tr] + (int64_t)a.tx_ord[li[q]];
+        if (a.kind == TI_OUTPUT_LEAF) {
+          if (t.live) static_cast<int32_t*>(a.out)[t.row * a.n_trees + tr] = a.exp_leaf_ids[lf];
+        } else if (!SPLIT) {   // (the host gives the split walk scalar leaves only)
+          add_leaf<ACC, KMAX>(acc, static_cast<const ACC*>(a.leaves) + lf * a.leaf_width, 0,
+                              a.leaf_width, a.tree_group[tr]);
+        }
+      }
+    }
+  }
+}
+
+struct TopU8Bins {   // the compact u8 bottom's top words: rank in byte 2
+  static constexpr bool kByteRank = true;
+  static __device__ __forceinline__ uint32_t bin(uint32_t nd, uint32_t lane_off) {
+    return lds_u8((nd & RxBins<true>::kNodeMask) | lane_off);
+  }
+  template <bool ZERO> static __device__ __forceinline__ bool right_slow(uint32_t nd, uint32_t b) {
+    return t8_right_slow<ZERO>(nd, b);
+  }
+};
+
+template <typename ACC, int KMAX, bool ZERO, bool SLOW, bool VIS, int ILP>
+__device__ __forceinline__ void t8_stage(const KArgs& a, ACC (&acc)[KMAX], int t0, int t1,
+                                         uint32_t sbase, const Tile& t, ACC (&pend)[ILP],
+                                         int (&pend_t)[ILP]) {
+  using W = RxBins<true>;
   rx_cu32* tx_off = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.rx_base));
   rx_cu32* tx_pos = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.tx_pos));
-  const int D0 = a.depth;
-  const uint32_t topb = 8u << D0;                   // 2^(D0+1) u32
+  const uint32_t topb = 8u << a.depth;   // 2^(D0+1) u32
+  const uint32_t lane_off = t.lane_off;
+  for (int j = t0; j < t1; j += ILP) {
+    uint32_t base[ILP], nd[ILP];
+#pragma unroll
+    for (int q = 0; q < ILP; ++q) {
+      const int tq = (j + q) < t1 ? (j + q) : (t1 - 1);
+      base[q] = sbase + tx_off[tq];
+    }
+    heap_top<ILP, SLOW, ZERO, TopU8Bins, PairLds>(base, a.depth, lane_off, nd);
+    uint32_t x[ILP];
+#pragma unroll
+    for (int q = 0; q < ILP; ++q) {
+      base[q] += topb;   // the bottom: u32 words by position
+      x[q] = *reinterpret_cast<const __attribute__((address_space(3))) uint32_t*>(
+          static_cast<uintptr_t>(base[q] + 4u * nd[q]));
+    }
+    for (;;) {
+      uint32_t all = x[0];
+#pragma unroll
+      for (int q = 1; q < ILP; ++q) all &= x[q];
+      if (__ballot((all & W::kLeaf) == 0u) == 0) break;   // every lane of every tree at a leaf
+      uint32_t b[ILP];
+      rx_u2_t pr[ILP];
+#pragma unroll
+      for (int q = 0; q < ILP; ++q) {
+        b[q] = lds_u8((x[q] & W::kNodeMask) | lane_off);
+        pr[q] = lx_rec(base[q] + ((x[q] >> 24) << 3));
+      }
+#pragma unroll
+      for (int q = 0; q < ILP; ++q) {
+        if (!SLOW) {
+          asm("v_cmp_lt_u32_sdwa vcc, %0, %1 src0_sel:BYTE_2 src1_sel:DWORD\n\t"
+              "v_cndmask_b32 %0, %2, %3, vcc"
+              : "+v"(x[q]) : "v"(b[q]), "v"(pr[q].x), "v"(pr[q].y) : "vcc");
+        } else {
+          x[q] = t8_right_slow<ZERO>(x[q], b[q]) ? pr[q].y : pr[q].x;
+        }
+      }
+    }
+    uint32_t li[ILP];   // the leaf's index in the position tables
+#pragma unroll
+    for (int q = 0; q < ILP; ++q) {
+      const int tq = (j + q) < t1 ? (j + q) : (t1 - 1);
+      li[q] = tx_pos[tq] + ((x[q] >> 23) & ~1u) + (((x[q] >> 16) & 0xFFu) == 0u ? 1u : 0u);
+    }
+    pos_leaves<ACC, KMAX, VIS, ILP, false>(a, acc, j, t1, li, t, pend, pend_t);
+  }
+}
+
+template <typename XT, typename ACC, int KMAX, bool ZERO, int ILP>
+__global__ void __launch_bounds__(512) t8explicit_predict_kernel(const KArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int PF = 8;   // = kLxPf (host): a stage is at most PF x 16 B x R
+  const Tile t = bin_tile(a, smem);
+  unsigned char* stage = smem + a.stage_off;
+  const TreeSpan<false, CopyU> sp(a, a.trees);
+  u32x4 pf[PF];
+  stage_first(sp, pf, t.tid, t.R);
+  const bool slow = rx_stage_bins<XT, ZERO, false, true>(t.flag, a, t.row0, t.R, t.tid, stage);
+  const bool vis = a.leaf_width == 1 && a.kind != TI_OUTPUT_LEAF;
+  ACC acc[KMAX];
+  init_acc(acc, a);
+  ACC pend[ILP];   // the previous group's leaf values (pos_leaves)
+  int pend_t[ILP];
+  pend_init(pend, pend_t);
+  for (int c = sp.first(); sp.more(c); c = sp.after(c)) {
+    const auto st = stage_step(sp, pf, stage, c, t.tid, t.R);
+    with_flags(slow, vis, [&](auto S, auto V) {
+      t8_stage<ACC, KMAX, ZERO, decltype(S)::value, decltype(V)::value, ILP>(a, acc, st.t0, st.t1, st.sbase,
+                                                                              t, pend, pend_t);
+    });
+  }
+  if (vis) t8_flush<ACC, KMAX, ILP>(a, acc, pend, pend_t);
+  if (!t.live || a.kind == TI_OUTPUT_LEAF) return;
+  finish_row<ACC, KMAX>(acc, a, t.row);
+}
+
+// ---- layout 9 with the compact u16 bottom (plan_tx16) -----------------------
+// The u8 compact bottom's step for u16 bins (C3: ~2,500 thresholds a feature).
+// A bottom node is one u32: rank in the high half (the compare reads WORD_1,
+// as the record walk's), the bin's byte offset in the low half with the lane
+// part cleared (bit 0 NaN-left, bit 1 the half-word, the word index above the
+// lane bits), and the children's pair index k' in bits 2-9 -- inside the lane
+// part, which the bin address masks off (a.bin_mask).  Children sit side by
+// side at positions 2k', 2k'+1, so a step is one LDS round trip (the u16 bin
+// and the 8-byte pair) and 5 VALU, against the record bottom's two round trips
+// and 7 VALU.  A leaf loops on itself (rank 0xFFFF at even positions: never
+// right, NaN-left; rank 0 at odd ones: always right, since every real bin is
+// >= 1 and a NaN takes the NaN-left bit) with bin offset 0, so a finished
+// lane reads its own column of word 0 (conflict-free, a real bin: a read of
+// anything else could return 0 and send an odd leaf to its sibling).  No
+// internal node has rank 0 or 0xFFFF (plan_tx16 checks), so the group's loop
+// ends when every tree's rank is one of those: (x + 0x10000) < 0x20000.  LightGBM's
+// zero flip has no bit left in the word: zero-missing forests keep one flag
+// bit per position in a 64-byte table between the top and the bottom, read by
+// the slow step (tiles holding an exact 0 or a NaN), which tracks the node's
+// position.  Leaf values come from the position tables as in t8_stage.
+constexpr uint32_t kT16ZfBytes = 64;   // zero-flip bits of <= 512 positions
+
+template <bool ZERO>
+__device__ __forceinline__ bool t16_right_slow(uint32_t x, uint32_t b, bool zf) {
+  constexpr uint32_t kNan = RxBins<false>::template nan_code<ZERO>();
+  bool right = (x >> 16) < b;
+  if (ZERO) right = right != (((b & 1u) != 0u) && zf);
+  if (b == kNan) right = (x & 1u) == 0u;
+  return right;
+}
+
+template <typename ACC, int KMAX, bool ZERO, bool SLOW, bool VIS, int ILP, bool SPLIT = false>
+__device__ __forceinline__ void t16_stage(const KArgs& a, ACC (&acc)[KMAX], int t0, int t1,
+                                          uint32_t sbase, const Tile& t, ACC (&pend)[ILP],
+                                          int (&pend_t)[ILP], int half = 0) {
+  rx_cu32* tx_off = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.rx_base));
+  rx_cu32* tx_pos = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.tx_pos));
+  const uint32_t topb = 8u << a.depth;              // 2^(D0+1) u32
   const uint32_t zfb = ZERO ? kT16ZfBytes : 0u;     // zero-flip bits before the bottom
   const uint32_t bmask = a.bin_mask;                // word index | half (the lane part cleared)
+  const uint32_t lane_off = t.lane_off;
   for (int jg = t0; jg < t1; jg += (SPLIT ? 2 : 1) * ILP) {
     const int j = SPLIT ? jg + half * ILP : jg;   // this lane's first tree of the group
-    uint32_t base[ILP], idx[ILP], nd[ILP], pos0[ILP];
+    uint32_t base[ILP], nd[ILP], pos0[ILP];
 #pragma unroll
     for (int q = 0; q < ILP; ++q) {
       // both halves' tree tables by wave-uniform indices (scalar loads), then
@@ -2349,11 +2417,19 @@ __device__ __forceinline__ void t16_stage(const KArgs& a, ACC (&acc)[KMAX], int 
         const uint32_t pa = tx_pos[ta], pb = tx_pos[tb];   // loads became one gather
         pos0[q] = half ? pb : pa;
       }
-      idx[q] = 1u;
-      nd[q] = *reinterpret_cast<const __attribute__((address_space(3))) uint32_t*>(
-          static_cast<uintptr_t>(base[q] + 4u));   // the root: one broadcast read per half
     }
-    for (int l = 0; l < D0; ++l) {   // the top, as layout 9's (record x words)
+    // The top, as layout 9's (record x words; one broadcast root read per
+    // half).  Its own copy of heap_top's walk: through heap_top the compiler
+    // keeps nd[] as scalars where this form gives it one vector, and
+    // t16split_predict_kernel<float, double, 16, true, 4> went from 101 to 104
+    // VGPRs (scripts/kernel_resources.py).
+    uint32_t idx[ILP];
+#pragma unroll
+    for (int q = 0; q < ILP; ++q) {
+      idx[q] = 1u;
+      nd[q] = lds_u32(base[q] + 4u);
+    }
+    for (int l = 0; l < a.depth; ++l) {
       uint32_t b[ILP];
       rx_u2_t pr[ILP];
 #pragma unroll
@@ -2420,30 +2496,7 @@ __device__ __forceinline__ void t16_stage(const KArgs& a, ACC (&acc)[KMAX], int 
       li[q] = (SPLIT ? pos0[q] : tx_pos[tq]) + ((x[q] >> 1) & 0x1FEu) +
               ((x[q] >> 16) == 0u ? 1u : 0u);
     }
-    if (VIS) {
-      // the previous group's leaves
-      if (SPLIT) t16_flush_split<ACC, KMAX, ILP>(a, acc, pend, pend_t);
-      else t8_flush<ACC, KMAX, ILP>(a, acc, pend, pend_t);
-#pragma unroll
-      for (int q = 0; q < ILP; ++q) {
-        pend[q] = static_cast<const ACC*>(a.tx_vals)[li[q]];
-        pend_t[q] = (j + q) < t1 ? (j + q) : -1;
-      }
-    } else {
-#pragma unroll
-      for (int q = 0; q < ILP; ++q) {
-        const int t = j + q;
-        if (t < t1) {
-          const int64_t lf = a.leaf_base[t] + (int64_t)a.tx_ord[li[q]];
-          if (a.kind == TI_OUTPUT_LEAF) {
-            if (live) static_cast<int32_t*>(a.out)[row * a.n_trees + t] = a.exp_leaf_ids[lf];
-          } else if (!SPLIT) {   // (the host gives the split walk scalar leaves only)
-            add_leaf<ACC, KMAX>(acc, static_cast<const ACC*>(a.leaves) + lf * a.leaf_width, 0,
-                                a.leaf_width, a.tree_group[t]);
-          }
-        }
-      }
-    }
+    pos_leaves<ACC, KMAX, VIS, ILP, SPLIT>(a, acc, j, t1, li, t, pend, pend_t);
   }
 }
 
@@ -2451,53 +2504,28 @@ template <typename XT, typename ACC, int KMAX, bool ZERO, int ILP>
 __global__ void __launch_bounds__(512) t16explicit_predict_kernel(const KArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int PF = 8;   // = kLxPf (host): a stage is at most PF x 16 B x R
-  const int R = blockDim.x;
-  const int tid = threadIdx.x;
-  const int64_t row0 = (int64_t)blockIdx.x * R;
-  const int64_t row = row0 + tid;
-  const bool live = row < a.n_rows;
-  volatile int* flag = reinterpret_cast<volatile int*>(smem + (size_t)a.bin_words * R * 4);
-  u32x4* stage = reinterpret_cast<u32x4*>(smem + a.stage_off);
-  const uint32_t lane_off = (uint32_t)tid * 4u;
-  rx_cu32* tx_off = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.rx_base));
-  rx_cu32* sst = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.stage_start));
-  const unsigned char* img = a.trees;
-  const int NS = a.n_stages;
-  auto lo_of = [&](int s) { return tx_off[sst[s]]; };   // trees start 16-byte aligned
-  auto n16_of = [&](int s) { return (int)((tx_off[sst[s + 1]] - tx_off[sst[s]]) >> 4); };
+  const Tile t = bin_tile(a, smem);
+  unsigned char* stage = smem + a.stage_off;
+  const TreeSpan<false, CopyU> sp(a, a.trees);
   u32x4 pf[PF];
-  prefetch_u<PF>(pf, reinterpret_cast<const u32x4*>(img + lo_of(0)), n16_of(0), tid, R);
-  const bool slow = rx_stage_bins<XT, ZERO, false, false>(flag, a, row0, R, tid, stage);
+  stage_first(sp, pf, t.tid, t.R);
+  const bool slow = rx_stage_bins<XT, ZERO, false, false>(t.flag, a, t.row0, t.R, t.tid, stage);
   const bool vis = a.leaf_width == 1 && a.kind != TI_OUTPUT_LEAF;
   ACC acc[KMAX];
   init_acc(acc, a);
   ACC pend[ILP];   // the previous group's leaf values
   int pend_t[ILP];
-#pragma unroll
-  for (int q = 0; q < ILP; ++q) {
-    pend[q] = ACC(0);
-    pend_t[q] = -1;
-  }
-  for (int s = 0; s < NS; ++s) {
-    const int t0 = (int)sst[s], t1 = (int)sst[s + 1];
-    const uint32_t lo = lo_of(s);
-    __syncthreads();   // the previous stage's walk is over
-    commit_u<PF>(pf, stage, n16_of(s), tid, R);
-    __syncthreads();
-    const int sn = s + 1 < NS ? s + 1 : s;
-    prefetch_u<PF>(pf, reinterpret_cast<const u32x4*>(img + lo_of(sn)), n16_of(sn), tid, R);
-    const uint32_t sbase = (uint32_t)a.stage_off - lo;   // LDS address = sbase + image byte
-    if (slow) {
-      if (vis) t16_stage<ACC, KMAX, ZERO, true, true, ILP>(a, acc, t0, t1, sbase, lane_off, row, live, pend, pend_t);
-      else t16_stage<ACC, KMAX, ZERO, true, false, ILP>(a, acc, t0, t1, sbase, lane_off, row, live, pend, pend_t);
-    } else {
-      if (vis) t16_stage<ACC, KMAX, ZERO, false, true, ILP>(a, acc, t0, t1, sbase, lane_off, row, live, pend, pend_t);
-      else t16_stage<ACC, KMAX, ZERO, false, false, ILP>(a, acc, t0, t1, sbase, lane_off, row, live, pend, pend_t);
-    }
+  pend_init(pend, pend_t);
+  for (int c = sp.first(); sp.more(c); c = sp.after(c)) {
+    const auto st = stage_step(sp, pf, stage, c, t.tid, t.R);
+    with_flags(slow, vis, [&](auto S, auto V) {
+      t16_stage<ACC, KMAX, ZERO, decltype(S)::value, decltype(V)::value, ILP>(a, acc, st.t0, st.t1, st.sbase,
+                                                                               t, pend, pend_t);
+    });
   }
   if (vis) t8_flush<ACC, KMAX, ILP>(a, acc, pend, pend_t);
-  if (!live || a.kind == TI_OUTPUT_LEAF) return;
-  finish_row<ACC, KMAX>(acc, a, row);
+  if (!t.live || a.kind == TI_OUTPUT_LEAF) return;
+  finish_row<ACC, KMAX>(acc, a, t.row);
 }
 
 // Two lanes a row (round 6): the R-row tile of the u16 compact
@@ -2512,61 +2540,43 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) t
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int PF = 4;   // 2R threads prefetch a stage of at most kLxPf x 16 B x R
   const int NT = blockDim.x;
-  const int R = NT >> 1;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
+  const int lane = threadIdx.x & 63;
   const int half = lane >> 5;
-  const int rloc = ((tid >> 6) << 5) | (lane & 31);   // the tile row of this lane pair
-  const int64_t row0 = (int64_t)blockIdx.x * R;
-  const int64_t row = row0 + rloc;
-  const bool live = row < a.n_rows;
-  volatile int* flag = reinterpret_cast<volatile int*>(smem + (size_t)a.bin_words * R * 4);
-  u32x4* stage = reinterpret_cast<u32x4*>(smem + a.stage_off);
-  const uint32_t lane_off = (uint32_t)rloc * 4u;
-  rx_cu32* tx_off = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.rx_base));
-  rx_cu32* sst = reinterpret_cast<rx_cu32*>(reinterpret_cast<uintptr_t>(a.stage_start));
-  const unsigned char* img = a.trees;
-  const int NS = a.n_stages;
-  auto lo_of = [&](int s) { return tx_off[sst[s]]; };   // trees start 16-byte aligned
-  auto n16_of = [&](int s) { return (int)((tx_off[sst[s + 1]] - tx_off[sst[s]]) >> 4); };
+  const int rloc = ((threadIdx.x >> 6) << 5) | (lane & 31);   // the tile row of this lane pair
+  Tile t;   // thread tid of 2R, on row rloc
+  t.R = NT >> 1;
+  t.tid = threadIdx.x;
+  t.row0 = (int64_t)blockIdx.x * t.R;
+  t.row = t.row0 + rloc;
+  t.live = t.row < a.n_rows;
+  t.flag = reinterpret_cast<volatile int*>(smem + (size_t)a.bin_words * t.R * 4);
+  t.lane_off = (uint32_t)rloc * 4u;
+  unsigned char* stage = smem + a.stage_off;
+  const TreeSpan<false, CopyU> sp(a, a.trees);
   // the first stage is fetched after the binning, not during it: the float64
   // binning's 5-ary search keeps 8 x 4 doubles in flight, and prefetch
   // registers live across it took the kernel past the 128 VGPRs 4 waves a
   // SIMD allow (138: 3 waves, one workgroup a CU); the exposed fetch is one
   // per tile, ~0.3 % of it
-  const bool slow = rx_stage_bins<XT, ZERO, false, false>(flag, a, row0, R, tid, stage, NT);
+  const bool slow = rx_stage_bins<XT, ZERO, false, false>(t.flag, a, t.row0, t.R, t.tid, stage, NT);
   u32x4 pf[PF];
-  prefetch_u<PF>(pf, reinterpret_cast<const u32x4*>(img + lo_of(0)), n16_of(0), tid, NT);
+  stage_first(sp, pf, t.tid, NT);
   const bool vis = a.leaf_width == 1 && a.kind != TI_OUTPUT_LEAF;
   ACC acc[KMAX];
   init_acc(acc, a);
   ACC pend[ILP];   // the previous group's leaf values (this lane's half)
   int pend_t[ILP];
-#pragma unroll
-  for (int q = 0; q < ILP; ++q) {
-    pend[q] = ACC(0);
-    pend_t[q] = -1;
-  }
-  for (int s = 0; s < NS; ++s) {
-    const int t0 = (int)sst[s], t1 = (int)sst[s + 1];
-    const uint32_t lo = lo_of(s);
-    __syncthreads();   // the previous stage's walk is over
-    commit_u<PF>(pf, stage, n16_of(s), tid, NT);
-    __syncthreads();
-    const int sn = s + 1 < NS ? s + 1 : s;
-    prefetch_u<PF>(pf, reinterpret_cast<const u32x4*>(img + lo_of(sn)), n16_of(sn), tid, NT);
-    const uint32_t sbase = (uint32_t)a.stage_off - lo;   // LDS address = sbase + image byte
-    if (slow) {
-      if (vis) t16_stage<ACC, KMAX, ZERO, true, true, ILP, true>(a, acc, t0, t1, sbase, lane_off, row, live, pend, pend_t, half);
-      else t16_stage<ACC, KMAX, ZERO, true, false, ILP, true>(a, acc, t0, t1, sbase, lane_off, row, live, pend, pend_t, half);
-    } else {
-      if (vis) t16_stage<ACC, KMAX, ZERO, false, true, ILP, true>(a, acc, t0, t1, sbase, lane_off, row, live, pend, pend_t, half);
-      else t16_stage<ACC, KMAX, ZERO, false, false, ILP, true>(a, acc, t0, t1, sbase, lane_off, row, live, pend, pend_t, half);
-    }
+  pend_init(pend, pend_t);
+  for (int c = sp.first(); sp.more(c); c = sp.after(c)) {
+    const auto st = stage_step(sp, pf, stage, c, t.tid, NT);
+    with_flags(slow, vis, [&](auto S, auto V) {
+      t16_stage<ACC, KMAX, ZERO, decltype(S)::value, decltype(V)::value, ILP, true>(
+          a, acc, st.t0, st.t1, st.sbase, t, pend, pend_t, half);
+    });
   }
   if (vis) t16_flush_split<ACC, KMAX, ILP>(a, acc, pend, pend_t);
-  if (!live || a.kind == TI_OUTPUT_LEAF || half) return;
-  finish_row<ACC, KMAX>(acc, a, row);
+  if (!t.live || a.kind == TI_OUTPUT_LEAF || half) return;
+  finish_row<ACC, KMAX>(acc, a, t.row);
 }
 
 }  // namespace ti
