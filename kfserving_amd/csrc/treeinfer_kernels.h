@@ -1124,6 +1124,28 @@ __device__ __forceinline__ uint32_t lds_u32(uint32_t byte_addr) {
 // ms (profiles/r3_c2_sroot_ab.jsonl); level 1's pair selected from the four
 // scalars of level 2 by level 0's decision was 5 % slower (its VALU selects
 // cost more than the LDS read they replace).
+//
+// What is not the per-visit step (4 VALU + 2 LDS per level) is trimmed by two
+// pieces, each with its macro so the earlier behaviour can be built for an A/B
+// (scripts/ab_fix_floor.py; the figures, and the pieces that lost, are in
+// DESIGN.md 3.1):
+//  * TI_FIX_PEEL (kernels of one output group): every stage that a full stage
+//    follows runs without the `cnt` guards, takes its tops by s_load_dwordx4
+//    at immediate offsets from one scalar offset bumped once a stage, and
+//    prefetches through a buffer resource at that scalar offset plus the
+//    lane's constant 16 tid: no address VALU.  The forest's last one or two
+//    stages keep the guarded, clamped form.
+//  * TI_FIX_L0 (those same stages, non-NaN tiles): level 0 without the two
+//    v_mov, as an arithmetic select: L ^ (((rank - bin) >> 31) & (L ^ R)),
+//    one SGPR operand an instruction (16.5 against 20.2 cycles a tree,
+//    scripts/micro/valu_rate.hip).  Exact because ranks and bins are below
+//    2^16, so the sign of the difference is rank < bin.
+#ifndef TI_FIX_PEEL
+#define TI_FIX_PEEL 1
+#endif
+#ifndef TI_FIX_L0
+#define TI_FIX_L0 1
+#endif
 typedef const __attribute__((address_space(4))) u32x4 fix_cu4_t;
 template <int NG>
 __device__ __forceinline__ void fix_tops(const KArgs& a, int t0, u32x4 (&top)[4 * NG]) {
@@ -1151,13 +1173,18 @@ __device__ __forceinline__ void fix_step(uint32_t& nd, uint32_t b, uint2 pr) {
         : "vcc", "scc");
   }
 }
-template <int KMAX, bool B16, bool CHECK_NAN, int NG>
+// FULL: a stage of 4 NG trees that another full stage follows (`nxt` is that
+// stage's byte offset in the forest, read through `rs`): no `cnt` guards, the
+// arithmetic level 0, and the next stage's prefetch issued from here.
+template <int KMAX, bool B16, bool CHECK_NAN, int NG, bool FULL = false>
 __device__ __forceinline__ void bheap_fix_stage(const KArgs& a, int cnt, int t0, float (&acc)[KMAX],
-                                                uint32_t lane_off, const u32x4 (&top)[4 * NG]) {
+                                                uint32_t lane_off, const u32x4 (&top)[4 * NG],
+                                                __amdgpu_buffer_rsrc_t rs, uint32_t nxt,
+                                                u32x4 (&pf)[NG], uint32_t lane16) {
   const uint32_t bmask = a.bin_mask;
 #pragma unroll
   for (int g = 0; g < NG; ++g) {
-    if (g * 4 >= cnt) break;   // uniform: the last stage may be short
+    if (!FULL && g * 4 >= cnt) break;   // uniform: the last stage may be short
     uint32_t nd[4];
 #if TI_FIX_SROOT
     {
@@ -1167,11 +1194,25 @@ __device__ __forceinline__ void bheap_fix_stage(const KArgs& a, int cnt, int t0,
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const u32x4 tp = top[g * 4 + q];
+        if (FULL && TI_FIX_L0 && !CHECK_NAN) {
+          asm("v_sub_u32 %0, %1, %2\n\t"
+              "v_ashrrev_i32 %0, 31, %0\n\t"
+              "v_and_b32 %0, %3, %0\n\t"
+              "v_xor_b32 %0, %4, %0"
+              : "=&v"(nd[q]) : "s"(tp.y >> 16), "v"(b0[q]), "s"(tp.z ^ tp.w), "s"(tp.z));
+          continue;
+        }
         // v_cmp against the scalar rank, two v_mov and a v_cndmask (with vcc
         // as the mask, gfx9's constant bus takes no SGPR source besides it)
         bool right = (tp.y >> 16) < b0[q];
         if (CHECK_NAN && (tp.y & 0x8000u)) right = right && b0[q] != BinTraits<B16>::kNan;
         nd[q] = right ? tp.w : tp.z;
+      }
+      // the next stage's prefetch, behind the last group's level 0
+      if (FULL && g == NG - 1) {
+#pragma unroll
+        for (int u = 0; u < NG; ++u)
+          pf[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, lane16 + (uint32_t)(u * kFixRows * 16), nxt, 0);
       }
     }
     constexpr int l_first = 1;
@@ -1196,7 +1237,7 @@ __device__ __forceinline__ void bheap_fix_stage(const KArgs& a, int cnt, int t0,
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int t = t0 + g * 4 + q;
-      if (g * 4 + q < cnt) {
+      if (FULL || g * 4 + q < cnt) {
         const float v = __uint_as_float(nd[q]);   // the leaf the last level selected
         add_leaf<float, KMAX>(acc, &v, 0, 1, KMAX == 1 ? 0 : a.tree_group[t]);
       }
@@ -1234,7 +1275,45 @@ __global__ void __launch_bounds__(512) bheap_fix_kernel(const KArgs a) {
   float acc[KMAX];
   init_acc(acc, a);
   u32x4 top[4 * NG] = {};
-  for (int t0 = 0; t0 < T; t0 += S) {
+  // the forest as a buffer resource (the peeled loop's reads; its size bounds them)
+  const int64_t forest_bytes = (int64_t)T * kFixTree;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<void*>(static_cast<const void*>(a.trees)), 0,
+      (int)(forest_bytes < 0x7fffffff ? forest_bytes : 0x7fffffff), 0x00020000);
+  int t0 = 0;
+#if TI_FIX_PEEL && TI_FIX_SROOT   // (the full stage's level 0 is the scalar root's)
+  // (one output group only: this loop's scalars took the kernels of 4 groups
+  // from 92 to 96 SGPRs and those of 16 from 64 to 66 VGPRs, either way from 8
+  // waves per SIMD to 7)
+  if (KMAX == 1 && 2 * S <= T && forest_bytes <= 0x7fffffff) {
+    // the stages that a full stage follows: everything in range, nothing
+    // clamped or guarded.  The forest is read through a buffer resource: a
+    // lane's part of a stage is at its constant offset 16 tid, the stage at
+    // the scalar offset `cur`, bumped once a stage -- no address VALU at all
+    // (and the resource bounds every read by the forest's size).
+    const uint32_t lane16 = (uint32_t)tid * 16u;
+    uint32_t cur = 0u;   // the current stage's byte offset in the forest
+    for (; t0 + 2 * S <= T; t0 += S) {
+      __syncthreads();
+      {
+        fix_cu4_t* tb = reinterpret_cast<fix_cu4_t*>(reinterpret_cast<uintptr_t>(a.trees) + cur);
+#pragma unroll
+        for (int i = 0; i < S; ++i) top[i] = tb[i * (kFixTree / 16)];
+      }
+#pragma unroll
+      for (int u = 0; u < NG; ++u) stage[tid + u * R] = pf[u];
+      __syncthreads();
+      const uint32_t nxt = cur + (uint32_t)(S * kFixTree);
+      // (the stage issues the prefetch of the next one, behind its level 0)
+      if (tile_nan)
+        bheap_fix_stage<KMAX, B16, true, NG, true>(a, S, t0, acc, lane_off, top, rs, nxt, pf, lane16);
+      else
+        bheap_fix_stage<KMAX, B16, false, NG, true>(a, S, t0, acc, lane_off, top, rs, nxt, pf, lane16);
+      cur = nxt;
+    }
+  }
+#endif
+  for (; t0 < T; t0 += S) {
     const int cnt = (T - t0) < S ? (T - t0) : S;
     __syncthreads();
 #if TI_FIX_SROOT
@@ -1252,9 +1331,9 @@ __global__ void __launch_bounds__(512) bheap_fix_kernel(const KArgs a) {
       }
     }
     if (tile_nan)
-      bheap_fix_stage<KMAX, B16, true, NG>(a, cnt, t0, acc, lane_off, top);
+      bheap_fix_stage<KMAX, B16, true, NG>(a, cnt, t0, acc, lane_off, top, rs, 0u, pf, 0u);
     else
-      bheap_fix_stage<KMAX, B16, false, NG>(a, cnt, t0, acc, lane_off, top);
+      bheap_fix_stage<KMAX, B16, false, NG>(a, cnt, t0, acc, lane_off, top, rs, 0u, pf, 0u);
   }
   if (!live) return;
   finish_row<float, KMAX>(acc, a, row);
