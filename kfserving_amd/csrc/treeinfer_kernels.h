@@ -1140,11 +1140,29 @@ __device__ __forceinline__ uint32_t lds_u32(uint32_t byte_addr) {
 //    one SGPR operand an instruction (16.5 against 20.2 cycles a tree,
 //    scripts/micro/valu_rate.hip).  Exact because ranks and bins are below
 //    2^16, so the sign of the difference is rank < bin.
+//
+// When a wave issues those instructions is set by a third piece:
+//  * TI_FIX_ROT: the four trees of a group are rotated against each other
+//    instead of walked as one batch a level.  A tree's step is followed at
+//    once by its own next level's two addresses and two reads (the bin read
+//    right before the pair read), so a step waits for its own pair alone,
+//    lgkmcnt(6), with the other three trees' six reads still in flight: no
+//    lgkmcnt(0) between level 1 and level 7, and the LDS array gets two reads
+//    a step instead of eight in a burst and then nothing for a round trip.
+//    The prologue is level 0 of tree q from the scalar tops, then q's level-1
+//    reads, in tree order; tree 0 finishes first, so the leaf adds keep their
+//    order.  The step and the two address VALU are one asm statement (the
+//    reads stay plain C++, so the compiler counts them): that keeps the order
+//    and leaves no boundary s_nop between the select and the addresses.  The
+//    same instructions as before, in another order.
 #ifndef TI_FIX_PEEL
 #define TI_FIX_PEEL 1
 #endif
 #ifndef TI_FIX_L0
 #define TI_FIX_L0 1
+#endif
+#ifndef TI_FIX_ROT
+#define TI_FIX_ROT 1
 #endif
 typedef const __attribute__((address_space(4))) u32x4 fix_cu4_t;
 template <int NG>
@@ -1173,6 +1191,35 @@ __device__ __forceinline__ void fix_step(uint32_t& nd, uint32_t b, uint2 pr) {
         : "vcc", "scc");
   }
 }
+// The rotated walk's step (TI_FIX_ROT): fix_step, then the next level's bin
+// address `ab` and pair offset `ap` of the same tree.
+template <bool B16, bool CHECK_NAN>
+__device__ __forceinline__ void fix_step_addr(uint32_t& nd, uint32_t b, uint2 pr, uint32_t bmask,
+                                              uint32_t lane_off, uint32_t& ab, uint32_t& ap) {
+  if (!CHECK_NAN) {
+    asm("v_cmp_lt_u32_sdwa vcc, %0, %3 src0_sel:WORD_1 src1_sel:DWORD\n\t"
+        "v_cndmask_b32 %0, %4, %5, vcc\n\t"
+        "v_and_or_b32 %1, %0, %6, %7\n\t"
+        "v_and_b32 %2, %8, %0"
+        : "+v"(nd), "=&v"(ab), "=&v"(ap)
+        : "v"(b), "v"(pr.x), "v"(pr.y), "s"(bmask), "v"(lane_off), "n"(kBNodePairMask)
+        : "vcc");
+  } else {
+    uint64_t mn, ml;
+    asm("v_cmp_lt_u32_sdwa vcc, %0, %5 src0_sel:WORD_1 src1_sel:DWORD\n\t"
+        "v_cmp_eq_u32_e64 %3, %8, %5\n\t"
+        "v_cmp_gt_i16_e64 %4, 0, %0\n\t"
+        "s_and_b64 %3, %3, %4\n\t"
+        "s_andn2_b64 vcc, vcc, %3\n\t"
+        "v_cndmask_b32 %0, %6, %7, vcc\n\t"
+        "v_and_or_b32 %1, %0, %9, %10\n\t"
+        "v_and_b32 %2, %11, %0"
+        : "+v"(nd), "=&v"(ab), "=&v"(ap), "=&s"(mn), "=&s"(ml)
+        : "v"(b), "v"(pr.x), "v"(pr.y), "s"(BinTraits<B16>::kNan), "s"(bmask), "v"(lane_off),
+          "n"(kBNodePairMask)
+        : "vcc", "scc");
+  }
+}
 // FULL: a stage of 4 NG trees that another full stage follows (`nxt` is that
 // stage's byte offset in the forest, read through `rs`): no `cnt` guards, the
 // arithmetic level 0, and the next stage's prefetch issued from here.
@@ -1187,35 +1234,96 @@ __device__ __forceinline__ void bheap_fix_stage(const KArgs& a, int cnt, int t0,
     if (!FULL && g * 4 >= cnt) break;   // uniform: the last stage may be short
     uint32_t nd[4];
 #if TI_FIX_SROOT
+#if TI_FIX_ROT
+    uint32_t b[4];
+    uint2 pr[4];
+#endif
     {
       uint32_t b0[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) b0[q] = lds_bin<B16>((top[g * 4 + q].y & bmask) | lane_off);
+#if TI_FIX_ROT
+      // the next stage's prefetch, issued with the root bin reads (the wave
+      // waits a round trip there anyway), never between a step and its reads
+      if (FULL && g == NG - 1) {
+#pragma unroll
+        for (int u = 0; u < NG; ++u)
+          pf[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, lane16 + (uint32_t)(u * kFixRows * 16), nxt, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#endif
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const u32x4 tp = top[g * 4 + q];
+#if TI_FIX_ROT
+        if (FULL && TI_FIX_L0 && !CHECK_NAN) {
+          // the arithmetic level 0 and tree q's level-1 addresses and reads
+          uint32_t ab, ap;
+          asm("v_sub_u32 %0, %3, %4\n\t"
+              "v_ashrrev_i32 %0, 31, %0\n\t"
+              "v_and_b32 %0, %5, %0\n\t"
+              "v_xor_b32 %0, %6, %0\n\t"
+              "v_and_or_b32 %1, %0, %7, %8\n\t"
+              "v_and_b32 %2, %9, %0"
+              : "=&v"(nd[q]), "=&v"(ab), "=&v"(ap)
+              : "s"(tp.y >> 16), "v"(b0[q]), "s"(tp.z ^ tp.w), "s"(tp.z), "s"(bmask), "v"(lane_off),
+                "n"(kBNodePairMask));
+          b[q] = lds_bin<B16>(ab);
+          pr[q] = lds_u2c(ap + (kFixStage + (uint32_t)((g * 4 + q) * kFixTree)));
+          __builtin_amdgcn_sched_barrier(0);
+          continue;
+        }
+#endif
         if (FULL && TI_FIX_L0 && !CHECK_NAN) {
           asm("v_sub_u32 %0, %1, %2\n\t"
               "v_ashrrev_i32 %0, 31, %0\n\t"
               "v_and_b32 %0, %3, %0\n\t"
               "v_xor_b32 %0, %4, %0"
               : "=&v"(nd[q]) : "s"(tp.y >> 16), "v"(b0[q]), "s"(tp.z ^ tp.w), "s"(tp.z));
-          continue;
+        } else {
+          // v_cmp against the scalar rank, two v_mov and a v_cndmask (with vcc
+          // as the mask, gfx9's constant bus takes no SGPR source besides it)
+          bool right = (tp.y >> 16) < b0[q];
+          if (CHECK_NAN && (tp.y & 0x8000u)) right = right && b0[q] != BinTraits<B16>::kNan;
+          nd[q] = right ? tp.w : tp.z;
         }
-        // v_cmp against the scalar rank, two v_mov and a v_cndmask (with vcc
-        // as the mask, gfx9's constant bus takes no SGPR source besides it)
-        bool right = (tp.y >> 16) < b0[q];
-        if (CHECK_NAN && (tp.y & 0x8000u)) right = right && b0[q] != BinTraits<B16>::kNan;
-        nd[q] = right ? tp.w : tp.z;
+#if TI_FIX_ROT
+        // the rotated walk's prologue: tree q's level-1 reads behind its level 0
+        b[q] = lds_bin<B16>((nd[q] & bmask) | lane_off);
+        pr[q] = lds_u2c((nd[q] & kBNodePairMask) + (kFixStage + (uint32_t)((g * 4 + q) * kFixTree)));
+        __builtin_amdgcn_sched_barrier(0);
+#endif
       }
+#if !TI_FIX_ROT
       // the next stage's prefetch, behind the last group's level 0
       if (FULL && g == NG - 1) {
 #pragma unroll
         for (int u = 0; u < NG; ++u)
           pf[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, lane16 + (uint32_t)(u * kFixRows * 16), nxt, 0);
       }
+#endif
     }
+#if TI_FIX_ROT
+    // levels 1..7, tree by tree: the step, then that tree's next two reads
+#pragma unroll
+    for (int l = 1; l < 8; ++l) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (l < 7) {
+          uint32_t ab, ap;
+          fix_step_addr<B16, CHECK_NAN>(nd[q], b[q], pr[q], bmask, lane_off, ab, ap);
+          b[q] = lds_bin<B16>(ab);
+          pr[q] = lds_u2c(ap + (kFixStage + (uint32_t)((g * 4 + q) * kFixTree)));
+        } else {
+          fix_step<B16, CHECK_NAN>(nd[q], b[q], pr[q]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    constexpr int l_first = 8;
+#else
     constexpr int l_first = 1;
+#endif
 #else
     (void)top;
 #pragma unroll
