@@ -344,8 +344,11 @@ int plan_launch(const ti_forest* f, const DeviceForest& d, int xdt, int kind, La
     } else {
       // fixed layout (bheap_fix_kernel): [bins][flag][NG groups of 4 trees at
       // kFixStage]; the binning goes through the stage area, 4 NG columns at a
-      // time.  NG = 1: 38,912 B, 4 workgroups (32 waves) per CU
+      // time.  NG = 1: 38,912 B, 4 workgroups (32 waves) per CU; where the
+      // kernel takes its two-buffer loop (ti::fix_dma_path: one output group,
+      // NG = 1, at least 8 trees) a second stage buffer: 47,104 B, 3 workgroups
       const int ng = std::min(2, std::max(1, env_int("TI_BHEAP_NG", 1)));
+      const int kmax = f->K == 1 ? 1 : f->K <= 4 ? 4 : 16;   // with_k_zero's buckets
       key.walk = ti::Walk::BinHeapFixed;
       key.groups = ng;
       a.stage_trees = 4 * ng;
@@ -353,7 +356,7 @@ int plan_launch(const ti_forest* f, const DeviceForest& d, int xdt, int kind, La
       a.bin_xpf = env_int("TI_BIN_XPF", 1) != 0;   // stage_bins' register path (NG = 1)
       a.stage_off = static_cast<int32_t>(ti::kFixStage);
       if (d.bh_fix_img != nullptr) a.trees = d.bh_fix_img;   // same walk, hot pair slots first
-      p->lds = ti::kFixStage + static_cast<size_t>(4 * ng) * ti::kFixTree;
+      p->lds = ti::fix_lds_bytes(kmax, ng, f->T);
     }
   } else if (is_record(f->layout)) {
     // record layouts: [bin image][flag][stage area (7, 8, 9)]

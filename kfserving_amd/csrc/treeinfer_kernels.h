@@ -1082,7 +1082,8 @@ __global__ void __launch_bounds__(512) bheap_predict_kernel(const KArgs a) {
 // ---- binned heap, fixed layout (C2: depth 8, scalar float leaves) ---------
 // The same walk with compile-time LDS addresses.  A tile is 512 rows; the LDS
 // is [bin image (<= 14 words x 2 KB)][flag @ kFixFlag][stage @ kFixStage: NG
-// groups of 4 tree records of 2 KB].  Tree q of group g sits at the constant
+// groups of 4 tree records of 2 KB; with TI_FIX_DMA a second 8 KB buffer
+// behind it for the one-group kernels].  Tree q of group g sits at the constant
 // kFixStage + (4 g + q) * 2048, so the children pair of the current node is
 // read at (nd & kBNodePairMask) + that constant (the node word carries its own
 // heap index in bits 3..10, pack_bheap): no index register and no address
@@ -1164,12 +1165,49 @@ __device__ __forceinline__ uint32_t lds_u32(uint32_t byte_addr) {
 #ifndef TI_FIX_ROT
 #define TI_FIX_ROT 1
 #endif
+// How a peeled stage reaches LDS is the fourth piece:
+//  * TI_FIX_DMA (the one-group kernels at 4 trees a stage): the peeled stages
+//    alternate between two LDS buffers, kFixStage and kFixStage2, and each
+//    wave fills its own 1 KiB slice of the next stage by LDS-DMA
+//    (buffer_load_dwordx4 ... offen lds through the loop's buffer resource,
+//    M0 = buffer + 1,024 x wave), so the image is byte for byte the forest's
+//    as before.  No pass through VGPRs, no ds_write_b128, and one barrier a
+//    stage instead of two (the order and why it is safe: at the loop).  The
+//    launch then takes 47,104 B of LDS, three workgroups a CU; kernel and host
+//    decide from fix_dma_path and size the launch by fix_lds_bytes.
+#ifndef TI_FIX_DMA
+#define TI_FIX_DMA 1
+#endif
+constexpr uint32_t kFixStage2 = kFixStage + 4u * (uint32_t)kFixTree;   // 38,912
+// Whether the launch of a kmax-group kernel at ng groups of 4 trees a stage
+// over n_trees trees runs the two-buffer loop (at least one peeled stage, the
+// forest within a buffer resource's 2 GB).
+__host__ __device__ constexpr bool fix_dma_path(int kmax, int ng, int64_t n_trees) {
+  return TI_FIX_DMA && TI_FIX_PEEL && TI_FIX_SROOT && TI_FIX_ROT && kmax == 1 && ng == 1 &&
+         8 * ng <= n_trees && n_trees * kFixTree <= 0x7fffffff;
+}
+// The dynamic LDS of that launch: bins, flag, and one stage or two buffers.
+__host__ __device__ constexpr size_t fix_lds_bytes(int kmax, int ng, int64_t n_trees) {
+  return fix_dma_path(kmax, ng, n_trees) ? (size_t)kFixStage2 + 4u * kFixTree
+                                         : (size_t)kFixStage + (size_t)(4 * ng) * kFixTree;
+}
 typedef const __attribute__((address_space(4))) u32x4 fix_cu4_t;
 template <int NG>
 __device__ __forceinline__ void fix_tops(const KArgs& a, int t0, u32x4 (&top)[4 * NG]) {
   fix_cu4_t* timg = reinterpret_cast<fix_cu4_t*>(reinterpret_cast<uintptr_t>(a.trees));
 #pragma unroll
   for (int i = 0; i < 4 * NG; ++i) top[i] = timg[min(t0 + i, a.n_trees - 1) * (kFixTree / 16)];
+}
+// A wave's 1 KiB slice (wave1k = 1,024 x its index, uniform) of the 8 KB stage
+// at byte `soff` of the forest behind `rs`, by LDS-DMA into the buffer at BUF:
+// lane tid's 16 bytes land at BUF + 16 tid, where the register stage wrote
+// them.  The builtin leaves M0 to the compiler.
+template <uint32_t BUF>
+__device__ __forceinline__ void fix_fill(__amdgpu_buffer_rsrc_t rs, uint32_t lane16, uint32_t soff,
+                                         uint32_t wave1k) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(
+      rs, reinterpret_cast<__attribute__((address_space(3))) void*>(static_cast<uintptr_t>(BUF + wave1k)),
+      16, lane16, soff, 0, 0);
 }
 template <bool B16, bool CHECK_NAN>
 __device__ __forceinline__ void fix_step(uint32_t& nd, uint32_t b, uint2 pr) {
@@ -1222,8 +1260,11 @@ __device__ __forceinline__ void fix_step_addr(uint32_t& nd, uint32_t b, uint2 pr
 }
 // FULL: a stage of 4 NG trees that another full stage follows (`nxt` is that
 // stage's byte offset in the forest, read through `rs`): no `cnt` guards, the
-// arithmetic level 0, and the next stage's prefetch issued from here.
-template <int KMAX, bool B16, bool CHECK_NAN, int NG, bool FULL = false>
+// arithmetic level 0, and the next stage's prefetch issued from here (not
+// with !PFETCH: the two-buffer loop issues its fill itself).  BASE is the LDS
+// buffer the stage is walked from, a constant in every pair read.
+template <int KMAX, bool B16, bool CHECK_NAN, int NG, bool FULL = false, uint32_t BASE = kFixStage,
+          bool PFETCH = true>
 __device__ __forceinline__ void bheap_fix_stage(const KArgs& a, int cnt, int t0, float (&acc)[KMAX],
                                                 uint32_t lane_off, const u32x4 (&top)[4 * NG],
                                                 __amdgpu_buffer_rsrc_t rs, uint32_t nxt,
@@ -1245,7 +1286,7 @@ __device__ __forceinline__ void bheap_fix_stage(const KArgs& a, int cnt, int t0,
 #if TI_FIX_ROT
       // the next stage's prefetch, issued with the root bin reads (the wave
       // waits a round trip there anyway), never between a step and its reads
-      if (FULL && g == NG - 1) {
+      if (FULL && PFETCH && g == NG - 1) {
 #pragma unroll
         for (int u = 0; u < NG; ++u)
           pf[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, lane16 + (uint32_t)(u * kFixRows * 16), nxt, 0);
@@ -1269,7 +1310,7 @@ __device__ __forceinline__ void bheap_fix_stage(const KArgs& a, int cnt, int t0,
               : "s"(tp.y >> 16), "v"(b0[q]), "s"(tp.z ^ tp.w), "s"(tp.z), "s"(bmask), "v"(lane_off),
                 "n"(kBNodePairMask));
           b[q] = lds_bin<B16>(ab);
-          pr[q] = lds_u2c(ap + (kFixStage + (uint32_t)((g * 4 + q) * kFixTree)));
+          pr[q] = lds_u2c(ap + (BASE + (uint32_t)((g * 4 + q) * kFixTree)));
           __builtin_amdgcn_sched_barrier(0);
           continue;
         }
@@ -1290,13 +1331,13 @@ __device__ __forceinline__ void bheap_fix_stage(const KArgs& a, int cnt, int t0,
 #if TI_FIX_ROT
         // the rotated walk's prologue: tree q's level-1 reads behind its level 0
         b[q] = lds_bin<B16>((nd[q] & bmask) | lane_off);
-        pr[q] = lds_u2c((nd[q] & kBNodePairMask) + (kFixStage + (uint32_t)((g * 4 + q) * kFixTree)));
+        pr[q] = lds_u2c((nd[q] & kBNodePairMask) + (BASE + (uint32_t)((g * 4 + q) * kFixTree)));
         __builtin_amdgcn_sched_barrier(0);
 #endif
       }
 #if !TI_FIX_ROT
       // the next stage's prefetch, behind the last group's level 0
-      if (FULL && g == NG - 1) {
+      if (FULL && PFETCH && g == NG - 1) {
 #pragma unroll
         for (int u = 0; u < NG; ++u)
           pf[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, lane16 + (uint32_t)(u * kFixRows * 16), nxt, 0);
@@ -1313,7 +1354,7 @@ __device__ __forceinline__ void bheap_fix_stage(const KArgs& a, int cnt, int t0,
           uint32_t ab, ap;
           fix_step_addr<B16, CHECK_NAN>(nd[q], b[q], pr[q], bmask, lane_off, ab, ap);
           b[q] = lds_bin<B16>(ab);
-          pr[q] = lds_u2c(ap + (kFixStage + (uint32_t)((g * 4 + q) * kFixTree)));
+          pr[q] = lds_u2c(ap + (BASE + (uint32_t)((g * 4 + q) * kFixTree)));
         } else {
           fix_step<B16, CHECK_NAN>(nd[q], b[q], pr[q]);
         }
@@ -1327,7 +1368,7 @@ __device__ __forceinline__ void bheap_fix_stage(const KArgs& a, int cnt, int t0,
 #else
     (void)top;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) nd[q] = lds_u32(kFixStage + (uint32_t)((g * 4 + q) * kFixTree) + 4u);
+    for (int q = 0; q < 4; ++q) nd[q] = lds_u32(BASE + (uint32_t)((g * 4 + q) * kFixTree) + 4u);
     constexpr int l_first = 0;
 #endif
 #pragma unroll
@@ -1337,7 +1378,7 @@ __device__ __forceinline__ void bheap_fix_stage(const KArgs& a, int cnt, int t0,
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         b[q] = lds_bin<B16>((nd[q] & bmask) | lane_off);
-        pr[q] = lds_u2c((nd[q] & kBNodePairMask) + (kFixStage + (uint32_t)((g * 4 + q) * kFixTree)));
+        pr[q] = lds_u2c((nd[q] & kBNodePairMask) + (BASE + (uint32_t)((g * 4 + q) * kFixTree)));
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q) fix_step<B16, CHECK_NAN>(nd[q], b[q], pr[q]);
@@ -1373,10 +1414,30 @@ __global__ void __launch_bounds__(512) bheap_fix_kernel(const KArgs a) {
   // first stage in flight while the tile is binned (a clamped lane re-reads
   // the forest's last word; its stage slot then holds a word no tree reads)
   u32x4 pf[NG];
+#if TI_FIX_DMA
+  // The two-buffer loop (below): stage 0 goes by LDS-DMA into the second
+  // buffer while the tile is binned (an unaligned batch bins through the
+  // first), and `pf` is loaded only where that loop hands over.
+  constexpr bool kDmaKernel = fix_dma_path(KMAX, NG, 8);   // (8 trees: the kernel can take it)
+  const bool dma = fix_dma_path(KMAX, NG, T);
+  uint32_t wave1k = 0u;   // the wave's 1 KiB slice of a stage
+  if constexpr (kDmaKernel) {
+    if (dma) {
+      wave1k = __builtin_amdgcn_readfirstlane(((uint32_t)tid >> 6) << 10);
+      fix_fill<kFixStage2>(__builtin_amdgcn_make_buffer_rsrc(
+                               const_cast<void*>(static_cast<const void*>(a.trees)), 0,
+                               (int)((int64_t)T * kFixTree), 0x00020000),
+                           (uint32_t)tid * 16u, 0u, wave1k);
+    }
+  }
+  if (!kDmaKernel || !dma)
+#endif
+  {
 #pragma unroll
-  for (int u = 0; u < NG; ++u) {
-    const int i = tid + u * R;
-    pf[u] = src[i < n16_all ? i : n16_all - 1];
+    for (int u = 0; u < NG; ++u) {
+      const int i = tid + u * R;
+      pf[u] = src[i < n16_all ? i : n16_all - 1];
+    }
   }
   const bool tile_nan = stage_bins<XT, B16, 4 * NG, (KMAX <= 4)>(
       flag, reinterpret_cast<XT*>(smem + kFixStage), a, row0, R, tid);
@@ -1393,6 +1454,66 @@ __global__ void __launch_bounds__(512) bheap_fix_kernel(const KArgs a) {
   // (one output group only: this loop's scalars took the kernels of 4 groups
   // from 92 to 96 SGPRs and those of 16 from 64 to 66 VGPRs, either way from 8
   // waves per SIMD to 7)
+#if TI_FIX_DMA
+  if constexpr (kDmaKernel) {
+    // The same stages from two LDS buffers filled by LDS-DMA, one barrier a
+    // stage.  Stage s sits in buffer (s + 1) & 1: stage 0 went into the second
+    // buffer before the binning.  Per stage s: the tops' scalar loads (ahead
+    // of the barrier, which covers their latency); s_waitcnt vmcnt(0) for the
+    // wave's own fill of s; the barrier; the fill of s + 1 into the other
+    // buffer; the walk of s.
+    //  * Read after write: every wave has waited for its own slice of s
+    //    before the barrier, and no wave reads s until it has passed that
+    //    barrier -- the read is one phase after the wait that retires the
+    //    DMA, which is the only order an LDS-DMA write has with a ds_read.
+    //  * Write after read: the other buffer held s - 1, and a wave that has
+    //    passed the barrier of s knows every wave has finished walking s - 1
+    //    (each walk ends with its last reads consumed), so the fill of s + 1
+    //    may land there at any time from here on.
+    // The last peeled stage issues no fill but the register prefetch of the
+    // first guarded stage; the guarded loop's first barrier then orders its
+    // ds_write into the first buffer behind this loop's last walk, whichever
+    // buffer that was in, and no DMA is in flight by then.
+    if (dma) {
+      const uint32_t lane16 = (uint32_t)tid * 16u;
+      uint32_t cur = 0u;   // the current stage's byte offset in the forest
+      auto one = [&](auto BUFC) -> bool {
+        constexpr uint32_t BUF = decltype(BUFC)::value;
+        constexpr uint32_t OTHER = BUF == kFixStage ? kFixStage2 : kFixStage;
+        const bool last = t0 + 3 * S > T;   // no peeled stage follows this one
+        {
+          fix_cu4_t* tb = reinterpret_cast<fix_cu4_t*>(reinterpret_cast<uintptr_t>(a.trees) + cur);
+#pragma unroll
+          for (int i = 0; i < S; ++i) top[i] = tb[i * (kFixTree / 16)];
+        }
+        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0) alone
+        // (the tops are in their SGPRs here: left alone, the compiler sinks
+        // the pure scalar loads behind the barrier, where their round trip is
+        // exposed once a stage)
+#pragma unroll
+        for (int i = 0; i < S; ++i) asm volatile("" : "+s"(top[i]));
+        __syncthreads();
+        const uint32_t nxt = cur + (uint32_t)(S * kFixTree);
+        if (last)
+          pf[0] = __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, nxt, 0);
+        else
+          fix_fill<OTHER>(rs, lane16, nxt, wave1k);
+        if (tile_nan)
+          bheap_fix_stage<KMAX, B16, true, NG, true, BUF, false>(a, S, t0, acc, lane_off, top, rs, nxt, pf,
+                                                                 lane16);
+        else
+          bheap_fix_stage<KMAX, B16, false, NG, true, BUF, false>(a, S, t0, acc, lane_off, top, rs, nxt, pf,
+                                                                  lane16);
+        cur = nxt;
+        t0 += S;
+        return last;
+      };
+      while (!one(std::integral_constant<uint32_t, kFixStage2>{}) &&
+             !one(std::integral_constant<uint32_t, kFixStage>{})) {
+      }
+    }
+  } else
+#endif
   if (KMAX == 1 && 2 * S <= T && forest_bytes <= 0x7fffffff) {
     // the stages that a full stage follows: everything in range, nothing
     // clamped or guarded.  The forest is read through a buffer resource: a
