@@ -1067,7 +1067,7 @@ int ti_forest_get_info(const ti_forest* f, ti_forest_info* info) {
                             : f->layout == kLayoutBinHeap ? f->bh[0].stride
                             : f->layout == kLayoutCatHeap ? pf->stride32 : 0;
   // walk id: the kernel variant a PMC pass was taken on (bench.py matches it)
-  info->walk = bheap_fixed(f, TI_F32, TI_OUTPUT_PREDICT) ? (TI_FIX_SROOT ? 2 : 1) : 0;
+  info->walk = bheap_fixed(f, TI_F32, TI_OUTPUT_PREDICT) ? 2 : 0;
   info->bin_bits = f->layout == kLayoutBinHeap ? (f->bh[0].b16 ? 16 : 8)
                    : is_record(f->layout) ? (f->rx[0].b8 ? 8 : 16) : 0;
   info->tree_ilp = f->layout == kLayoutRecord ? f->rx_ilp : f->layout == kLayoutHeapTop ? f->hx_ilp

@@ -35,9 +35,6 @@
 #ifndef TI_TILP
 #define TI_TILP 8   // trees walked concurrently per lane (heap layout)
 #endif
-#ifndef TI_ASM_STEP
-#define TI_ASM_STEP 1   // binned heap: hand-scheduled compare/select/carry step
-#endif
 #ifndef TI_EXP_ILP
 #define TI_EXP_ILP 4    // trees walked concurrently per lane (explicit kernels)
 #endif
@@ -692,13 +689,6 @@ template <bool B16> struct BinTraits;
 template <> struct BinTraits<true> { static constexpr int P = 2; static constexpr uint32_t kNan = 0xFFFFu; };
 template <> struct BinTraits<false> { static constexpr int P = 4; static constexpr uint32_t kNan = 0xFFu; };
 
-template <bool B16, bool CHECK_NAN>
-__device__ __forceinline__ bool bin_left(uint32_t b, uint32_t nd) {
-  bool left = b <= (nd >> 16);
-  if (CHECK_NAN) left = left || (b == BinTraits<B16>::kNan && (nd & kBNodeNanLeft) != 0u);
-  return left;
-}
-
 template <bool B16>
 __device__ __forceinline__ uint32_t lds_bin(uint32_t byte_addr) {
   if (B16)
@@ -954,6 +944,17 @@ __device__ __forceinline__ bool stage_bins(volatile int* flag, XT* temp, const K
   return *flag != 0;
 }
 
+// The NaN tiles' decision, shared by the asm steps below: vcc = right =
+// (rank < bin) && !(bin == NaN code && NaN-left), NaN-left being bit 15 = the
+// sign of the node's low half as i16.  Operands nd, b, nan (the bin width's
+// NaN code, an SGPR) and two scratch SGPR pairs mn, ml; clobbers vcc and scc.
+#define TI_ASM_NAN_RIGHT                                                     \
+  "v_cmp_lt_u32_sdwa vcc, %[nd], %[b] src0_sel:WORD_1 src1_sel:DWORD\n\t"    \
+  "v_cmp_eq_u32_e64 %[mn], %[nan], %[b]\n\t"                                 \
+  "v_cmp_gt_i16_e64 %[ml], 0, %[nd]\n\t"                                     \
+  "s_and_b64 %[mn], %[mn], %[ml]\n\t"                                        \
+  "s_andn2_b64 vcc, vcc, %[mn]\n\t"
+
 // Walk one LDS stage of binned complete trees.  A tree record is 2^D u32
 // entries (1-based heap: node i has children 2i and 2i+1; entry 0 unused),
 // then 2^D * leaf_width leaves (ACC).  At each level a lane issues the bin
@@ -991,16 +992,7 @@ __device__ __forceinline__ void bheap_stage(const KArgs& a, const unsigned char*
       }
 #pragma unroll
       for (int q = 0; q < kBTilp; ++q) {
-#if TI_ASM_STEP == 2
-        if (!CHECK_NAN) {
-          uint64_t m;
-          asm("v_cmp_lt_u32_sdwa %2, %0, %3 src0_sel:WORD_1 src1_sel:DWORD\n\t"
-              "v_cndmask_b32_e64 %0, %4, %5, %2\n\t"
-              "v_addc_co_u32_e64 %1, %2, %1, %1, %2"
-              : "+v"(nd[q]), "+v"(idx[q]), "=&s"(m) : "v"(b[q]), "v"(pr[q].x), "v"(pr[q].y));
-          continue;
-        }
-#elif TI_ASM_STEP
+        // the hand-scheduled compare / select / carry step
         if (!CHECK_NAN) {
           // right = rank < bin (SDWA compare on the node's high half), then the
           // child select and idx = 2 idx + right as one carry-in add: 3 VALU
@@ -1009,28 +1001,16 @@ __device__ __forceinline__ void bheap_stage(const KArgs& a, const unsigned char*
               "v_addc_co_u32 %1, vcc, %1, %1, vcc"
               : "+v"(nd[q]), "+v"(idx[q]) : "v"(b[q]), "v"(pr[q].x), "v"(pr[q].y)
               : "vcc");
-          continue;
         } else {
-          // NaN tiles: right = (rank < bin) && !(bin == NaN code && NaN-left),
-          // NaN-left being bit 15 = the sign of the node's low half as i16.
-          // 5 VALU (the compiler's form: 9) and two SALU mask ops.
+          // NaN tiles: 5 VALU (the compiler's form: 9) and two SALU mask ops
           uint64_t mn, ml;
-          asm("v_cmp_lt_u32_sdwa vcc, %0, %4 src0_sel:WORD_1 src1_sel:DWORD\n\t"
-              "v_cmp_eq_u32_e64 %2, %7, %4\n\t"
-              "v_cmp_gt_i16_e64 %3, 0, %0\n\t"
-              "s_and_b64 %2, %2, %3\n\t"
-              "s_andn2_b64 vcc, vcc, %2\n\t"
-              "v_cndmask_b32 %0, %5, %6, vcc\n\t"
-              "v_addc_co_u32 %1, vcc, %1, %1, vcc"
-              : "+v"(nd[q]), "+v"(idx[q]), "=&s"(mn), "=&s"(ml)
-              : "v"(b[q]), "v"(pr[q].x), "v"(pr[q].y), "s"(BinTraits<B16>::kNan)
+          asm(TI_ASM_NAN_RIGHT
+              "v_cndmask_b32 %[nd], %[l], %[r], vcc\n\t"
+              "v_addc_co_u32 %[idx], vcc, %[idx], %[idx], vcc"
+              : [nd] "+v"(nd[q]), [idx] "+v"(idx[q]), [mn] "=&s"(mn), [ml] "=&s"(ml)
+              : [b] "v"(b[q]), [l] "v"(pr[q].x), [r] "v"(pr[q].y), [nan] "s"(BinTraits<B16>::kNan)
               : "vcc", "scc");
-          continue;
         }
-#endif
-        const bool right = !bin_left<B16, CHECK_NAN>(b[q], nd[q]);
-        idx[q] = idx[q] + idx[q] + (uint32_t)right;
-        nd[q] = right ? pr[q].y : pr[q].x;
       }
     }
 #pragma unroll
@@ -1082,8 +1062,8 @@ __global__ void __launch_bounds__(512) bheap_predict_kernel(const KArgs a) {
 // ---- binned heap, fixed layout (C2: depth 8, scalar float leaves) ---------
 // The same walk with compile-time LDS addresses.  A tile is 512 rows; the LDS
 // is [bin image (<= 14 words x 2 KB)][flag @ kFixFlag][stage @ kFixStage: NG
-// groups of 4 tree records of 2 KB; with TI_FIX_DMA a second 8 KB buffer
-// behind it for the one-group kernels].  Tree q of group g sits at the constant
+// groups of 4 tree records of 2 KB; a second 8 KB buffer behind it for the
+// two-buffer loop of the one-group kernels].  Tree q of group g sits at the constant
 // kFixStage + (4 g + q) * 2048, so the children pair of the current node is
 // read at (nd & kBNodePairMask) + that constant (the node word carries its own
 // heap index in bits 3..10, pack_bheap): no index register and no address
@@ -1113,40 +1093,30 @@ __device__ __forceinline__ uint32_t lds_u32(uint32_t byte_addr) {
       static_cast<uintptr_t>(byte_addr));
 }
 
-#ifndef TI_FIX_SROOT
-#define TI_FIX_SROOT 1
-#endif
-// SROOT: the root and its children pair are the same for every lane, so words
-// 0..3 of each tree's image come as scalar loads from global memory, issued
-// between the two barriers of the stage commit (whose LDS wait covers their
-// latency; a scalar load still in flight would make every LDS wait of the walk
-// wait for it), and level 0 is the bin read, a compare against the scalar rank
-// and a select between two scalars: no pair read from LDS.  C2 0.787 -> 0.775
-// ms (profiles/r3_c2_sroot_ab.jsonl); level 1's pair selected from the four
-// scalars of level 2 by level 0's decision was 5 % slower (its VALU selects
-// cost more than the LDS read they replace).
-//
-// What is not the per-visit step (4 VALU + 2 LDS per level) is trimmed by two
-// pieces, each with its macro so the earlier behaviour can be built for an A/B
-// (scripts/ab_fix_floor.py; the figures, and the pieces that lost, are in
-// DESIGN.md 3.1):
-//  * TI_FIX_PEEL (kernels of one output group): every stage that a full stage
-//    follows runs without the `cnt` guards, takes its tops by s_load_dwordx4
-//    at immediate offsets from one scalar offset bumped once a stage, and
-//    prefetches through a buffer resource at that scalar offset plus the
-//    lane's constant 16 tid: no address VALU.  The forest's last one or two
-//    stages keep the guarded, clamped form.
-//  * TI_FIX_L0 (those same stages, non-NaN tiles): level 0 without the two
-//    v_mov, as an arithmetic select: L ^ (((rank - bin) >> 31) & (L ^ R)),
-//    one SGPR operand an instruction (16.5 against 20.2 cycles a tree,
-//    scripts/micro/valu_rate.hip).  Exact because ranks and bins are below
-//    2^16, so the sign of the difference is rank < bin.
-//
-// When a wave issues those instructions is set by a third piece:
-//  * TI_FIX_ROT: the four trees of a group are rotated against each other
-//    instead of walked as one batch a level.  A tree's step is followed at
-//    once by its own next level's two addresses and two reads (the bin read
-//    right before the pair read), so a step waits for its own pair alone,
+// How the walk is built on top of that level (the measured figures, and the
+// pieces that were tried and lost, are in DESIGN.md 3.1):
+//  * The scalar root.  The root and its children pair are the same for every
+//    lane, so words 0..3 of each tree's image (`top`) come as scalar loads
+//    from global memory, issued where a barrier of the stage covers their
+//    latency (a scalar load still in flight would make every LDS wait of the
+//    walk wait for it), and level 0 is the bin read, a compare against the
+//    scalar rank and a select between two scalars: no pair read from LDS.
+//  * Peeled stages (kernels of one output group).  Every stage that a full
+//    stage follows runs without the `cnt` guards, takes its tops by
+//    s_load_dwordx4 at immediate offsets from one scalar offset bumped once a
+//    stage, and reads the forest through a buffer resource at that scalar
+//    offset plus the lane's constant 16 tid: no address VALU.  The forest's
+//    last one or two stages keep the guarded, clamped form, as do all stages
+//    of the kernels of more groups (the peeled loop's scalars cost those a
+//    wave per SIMD).
+//  * The arithmetic level 0 (peeled stages, NaN-free tiles): level 0 without
+//    the two v_mov, L ^ (((rank - bin) >> 31) & (L ^ R)), one SGPR operand an
+//    instruction.  Exact because ranks and bins are below 2^16, so the sign of
+//    the difference is rank < bin.
+//  * The rotation.  The four trees of a group are rotated against each other,
+//    not walked as one batch a level.  A tree's step is followed at once by
+//    its own next level's two addresses and two reads (the bin read right
+//    before the pair read), so a step waits for its own pair alone,
 //    lgkmcnt(6), with the other three trees' six reads still in flight: no
 //    lgkmcnt(0) between level 1 and level 7, and the LDS array gets two reads
 //    a step instead of eight in a burst and then nothing for a round trip.
@@ -1154,37 +1124,27 @@ __device__ __forceinline__ uint32_t lds_u32(uint32_t byte_addr) {
 //    reads, in tree order; tree 0 finishes first, so the leaf adds keep their
 //    order.  The step and the two address VALU are one asm statement (the
 //    reads stay plain C++, so the compiler counts them): that keeps the order
-//    and leaves no boundary s_nop between the select and the addresses.  The
-//    same instructions as before, in another order.
-#ifndef TI_FIX_PEEL
-#define TI_FIX_PEEL 1
-#endif
-#ifndef TI_FIX_L0
-#define TI_FIX_L0 1
-#endif
-#ifndef TI_FIX_ROT
-#define TI_FIX_ROT 1
-#endif
-// How a peeled stage reaches LDS is the fourth piece:
-//  * TI_FIX_DMA (the one-group kernels at 4 trees a stage): the peeled stages
-//    alternate between two LDS buffers, kFixStage and kFixStage2, and each
-//    wave fills its own 1 KiB slice of the next stage by LDS-DMA
+//    and leaves no boundary s_nop between the select and the addresses.
+//  * The two-buffer LDS-DMA loop (the one-group kernels at 4 trees a stage,
+//    NG = 1, on forests of at least 8 trees: fix_dma_path).  The peeled
+//    stages alternate between two LDS buffers, kFixStage and kFixStage2, and
+//    each wave fills its own 1 KiB slice of the next stage by LDS-DMA
 //    (buffer_load_dwordx4 ... offen lds through the loop's buffer resource,
-//    M0 = buffer + 1,024 x wave), so the image is byte for byte the forest's
-//    as before.  No pass through VGPRs, no ds_write_b128, and one barrier a
-//    stage instead of two (the order and why it is safe: at the loop).  The
-//    launch then takes 47,104 B of LDS, three workgroups a CU; kernel and host
-//    decide from fix_dma_path and size the launch by fix_lds_bytes.
-#ifndef TI_FIX_DMA
-#define TI_FIX_DMA 1
-#endif
+//    M0 = buffer + 1,024 x wave), so the image is byte for byte the forest's.
+//    No pass through VGPRs, no ds_write_b128, and one barrier a stage instead
+//    of two (the order and why it is safe: at the loop).  The launch then
+//    takes 47,104 B of LDS, three workgroups a CU; kernel and host decide from
+//    fix_dma_path and size the launch by fix_lds_bytes.
+// So the one-group kernels run, at NG = 1, the two-buffer loop and then the
+// guarded stages; at NG = 2, the peeled loop staged through registers (two
+// barriers a stage) and then the guarded stages; the kernels of 4 and 16
+// groups run guarded stages alone.
 constexpr uint32_t kFixStage2 = kFixStage + 4u * (uint32_t)kFixTree;   // 38,912
 // Whether the launch of a kmax-group kernel at ng groups of 4 trees a stage
 // over n_trees trees runs the two-buffer loop (at least one peeled stage, the
 // forest within a buffer resource's 2 GB).
 __host__ __device__ constexpr bool fix_dma_path(int kmax, int ng, int64_t n_trees) {
-  return TI_FIX_DMA && TI_FIX_PEEL && TI_FIX_SROOT && TI_FIX_ROT && kmax == 1 && ng == 1 &&
-         8 * ng <= n_trees && n_trees * kFixTree <= 0x7fffffff;
+  return kmax == 1 && ng == 1 && 8 * ng <= n_trees && n_trees * kFixTree <= 0x7fffffff;
 }
 // The dynamic LDS of that launch: bins, flag, and one stage or two buffers.
 __host__ __device__ constexpr size_t fix_lds_bytes(int kmax, int ng, int64_t n_trees) {
@@ -1216,20 +1176,15 @@ __device__ __forceinline__ void fix_step(uint32_t& nd, uint32_t b, uint2 pr) {
         "v_cndmask_b32 %0, %2, %3, vcc"
         : "+v"(nd) : "v"(b), "v"(pr.x), "v"(pr.y) : "vcc");
   } else {
-    // right = (rank < bin) && !(bin == NaN code && NaN-left (bit 15))
     uint64_t mn, ml;
-    asm("v_cmp_lt_u32_sdwa vcc, %0, %3 src0_sel:WORD_1 src1_sel:DWORD\n\t"
-        "v_cmp_eq_u32_e64 %1, %6, %3\n\t"
-        "v_cmp_gt_i16_e64 %2, 0, %0\n\t"
-        "s_and_b64 %1, %1, %2\n\t"
-        "s_andn2_b64 vcc, vcc, %1\n\t"
-        "v_cndmask_b32 %0, %4, %5, vcc"
-        : "+v"(nd), "=&s"(mn), "=&s"(ml)
-        : "v"(b), "v"(pr.x), "v"(pr.y), "s"(BinTraits<B16>::kNan)
+    asm(TI_ASM_NAN_RIGHT
+        "v_cndmask_b32 %[nd], %[l], %[r], vcc"
+        : [nd] "+v"(nd), [mn] "=&s"(mn), [ml] "=&s"(ml)
+        : [b] "v"(b), [l] "v"(pr.x), [r] "v"(pr.y), [nan] "s"(BinTraits<B16>::kNan)
         : "vcc", "scc");
   }
 }
-// The rotated walk's step (TI_FIX_ROT): fix_step, then the next level's bin
+// The rotated walk's step: fix_step, then the next level's bin
 // address `ab` and pair offset `ap` of the same tree.
 template <bool B16, bool CHECK_NAN>
 __device__ __forceinline__ void fix_step_addr(uint32_t& nd, uint32_t b, uint2 pr, uint32_t bmask,
@@ -1244,17 +1199,13 @@ __device__ __forceinline__ void fix_step_addr(uint32_t& nd, uint32_t b, uint2 pr
         : "vcc");
   } else {
     uint64_t mn, ml;
-    asm("v_cmp_lt_u32_sdwa vcc, %0, %5 src0_sel:WORD_1 src1_sel:DWORD\n\t"
-        "v_cmp_eq_u32_e64 %3, %8, %5\n\t"
-        "v_cmp_gt_i16_e64 %4, 0, %0\n\t"
-        "s_and_b64 %3, %3, %4\n\t"
-        "s_andn2_b64 vcc, vcc, %3\n\t"
-        "v_cndmask_b32 %0, %6, %7, vcc\n\t"
-        "v_and_or_b32 %1, %0, %9, %10\n\t"
-        "v_and_b32 %2, %11, %0"
-        : "+v"(nd), "=&v"(ab), "=&v"(ap), "=&s"(mn), "=&s"(ml)
-        : "v"(b), "v"(pr.x), "v"(pr.y), "s"(BinTraits<B16>::kNan), "s"(bmask), "v"(lane_off),
-          "n"(kBNodePairMask)
+    asm(TI_ASM_NAN_RIGHT
+        "v_cndmask_b32 %[nd], %[l], %[r], vcc\n\t"
+        "v_and_or_b32 %[ab], %[nd], %[bmask], %[lane]\n\t"
+        "v_and_b32 %[ap], %[pmask], %[nd]"
+        : [nd] "+v"(nd), [ab] "=&v"(ab), [ap] "=&v"(ap), [mn] "=&s"(mn), [ml] "=&s"(ml)
+        : [b] "v"(b), [l] "v"(pr.x), [r] "v"(pr.y), [nan] "s"(BinTraits<B16>::kNan),
+          [bmask] "s"(bmask), [lane] "v"(lane_off), [pmask] "n"(kBNodePairMask)
         : "vcc", "scc");
   }
 }
@@ -1273,17 +1224,12 @@ __device__ __forceinline__ void bheap_fix_stage(const KArgs& a, int cnt, int t0,
 #pragma unroll
   for (int g = 0; g < NG; ++g) {
     if (!FULL && g * 4 >= cnt) break;   // uniform: the last stage may be short
-    uint32_t nd[4];
-#if TI_FIX_SROOT
-#if TI_FIX_ROT
-    uint32_t b[4];
+    uint32_t nd[4], b[4];
     uint2 pr[4];
-#endif
     {
       uint32_t b0[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) b0[q] = lds_bin<B16>((top[g * 4 + q].y & bmask) | lane_off);
-#if TI_FIX_ROT
       // the next stage's prefetch, issued with the root bin reads (the wave
       // waits a round trip there anyway), never between a step and its reads
       if (FULL && PFETCH && g == NG - 1) {
@@ -1292,12 +1238,11 @@ __device__ __forceinline__ void bheap_fix_stage(const KArgs& a, int cnt, int t0,
           pf[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, lane16 + (uint32_t)(u * kFixRows * 16), nxt, 0);
       }
       __builtin_amdgcn_sched_barrier(0);
-#endif
+      // the prologue: level 0 of tree q from its scalar top, then q's level-1 reads
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const u32x4 tp = top[g * 4 + q];
-#if TI_FIX_ROT
-        if (FULL && TI_FIX_L0 && !CHECK_NAN) {
+        if (FULL && !CHECK_NAN) {
           // the arithmetic level 0 and tree q's level-1 addresses and reads
           uint32_t ab, ap;
           asm("v_sub_u32 %0, %3, %4\n\t"
@@ -1311,40 +1256,18 @@ __device__ __forceinline__ void bheap_fix_stage(const KArgs& a, int cnt, int t0,
                 "n"(kBNodePairMask));
           b[q] = lds_bin<B16>(ab);
           pr[q] = lds_u2c(ap + (BASE + (uint32_t)((g * 4 + q) * kFixTree)));
-          __builtin_amdgcn_sched_barrier(0);
-          continue;
-        }
-#endif
-        if (FULL && TI_FIX_L0 && !CHECK_NAN) {
-          asm("v_sub_u32 %0, %1, %2\n\t"
-              "v_ashrrev_i32 %0, 31, %0\n\t"
-              "v_and_b32 %0, %3, %0\n\t"
-              "v_xor_b32 %0, %4, %0"
-              : "=&v"(nd[q]) : "s"(tp.y >> 16), "v"(b0[q]), "s"(tp.z ^ tp.w), "s"(tp.z));
         } else {
           // v_cmp against the scalar rank, two v_mov and a v_cndmask (with vcc
           // as the mask, gfx9's constant bus takes no SGPR source besides it)
           bool right = (tp.y >> 16) < b0[q];
           if (CHECK_NAN && (tp.y & 0x8000u)) right = right && b0[q] != BinTraits<B16>::kNan;
           nd[q] = right ? tp.w : tp.z;
+          b[q] = lds_bin<B16>((nd[q] & bmask) | lane_off);
+          pr[q] = lds_u2c((nd[q] & kBNodePairMask) + (BASE + (uint32_t)((g * 4 + q) * kFixTree)));
         }
-#if TI_FIX_ROT
-        // the rotated walk's prologue: tree q's level-1 reads behind its level 0
-        b[q] = lds_bin<B16>((nd[q] & bmask) | lane_off);
-        pr[q] = lds_u2c((nd[q] & kBNodePairMask) + (BASE + (uint32_t)((g * 4 + q) * kFixTree)));
         __builtin_amdgcn_sched_barrier(0);
-#endif
       }
-#if !TI_FIX_ROT
-      // the next stage's prefetch, behind the last group's level 0
-      if (FULL && PFETCH && g == NG - 1) {
-#pragma unroll
-        for (int u = 0; u < NG; ++u)
-          pf[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, lane16 + (uint32_t)(u * kFixRows * 16), nxt, 0);
-      }
-#endif
     }
-#if TI_FIX_ROT
     // levels 1..7, tree by tree: the step, then that tree's next two reads
 #pragma unroll
     for (int l = 1; l < 8; ++l) {
@@ -1360,28 +1283,6 @@ __device__ __forceinline__ void bheap_fix_stage(const KArgs& a, int cnt, int t0,
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-    }
-    constexpr int l_first = 8;
-#else
-    constexpr int l_first = 1;
-#endif
-#else
-    (void)top;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) nd[q] = lds_u32(BASE + (uint32_t)((g * 4 + q) * kFixTree) + 4u);
-    constexpr int l_first = 0;
-#endif
-#pragma unroll
-    for (int l = l_first; l < 8; ++l) {
-      uint32_t b[4];
-      uint2 pr[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        b[q] = lds_bin<B16>((nd[q] & bmask) | lane_off);
-        pr[q] = lds_u2c((nd[q] & kBNodePairMask) + (BASE + (uint32_t)((g * 4 + q) * kFixTree)));
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) fix_step<B16, CHECK_NAN>(nd[q], b[q], pr[q]);
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -1414,7 +1315,6 @@ __global__ void __launch_bounds__(512) bheap_fix_kernel(const KArgs a) {
   // first stage in flight while the tile is binned (a clamped lane re-reads
   // the forest's last word; its stage slot then holds a word no tree reads)
   u32x4 pf[NG];
-#if TI_FIX_DMA
   // The two-buffer loop (below): stage 0 goes by LDS-DMA into the second
   // buffer while the tile is binned (an unaligned batch bins through the
   // first), and `pf` is loaded only where that loop hands over.
@@ -1430,9 +1330,7 @@ __global__ void __launch_bounds__(512) bheap_fix_kernel(const KArgs a) {
                            (uint32_t)tid * 16u, 0u, wave1k);
     }
   }
-  if (!kDmaKernel || !dma)
-#endif
-  {
+  if (!kDmaKernel || !dma) {
 #pragma unroll
     for (int u = 0; u < NG; ++u) {
       const int i = tid + u * R;
@@ -1450,11 +1348,12 @@ __global__ void __launch_bounds__(512) bheap_fix_kernel(const KArgs a) {
       const_cast<void*>(static_cast<const void*>(a.trees)), 0,
       (int)(forest_bytes < 0x7fffffff ? forest_bytes : 0x7fffffff), 0x00020000);
   int t0 = 0;
-#if TI_FIX_PEEL && TI_FIX_SROOT   // (the full stage's level 0 is the scalar root's)
-  // (one output group only: this loop's scalars took the kernels of 4 groups
-  // from 92 to 96 SGPRs and those of 16 from 64 to 66 VGPRs, either way from 8
-  // waves per SIMD to 7)
-#if TI_FIX_DMA
+  // The peeled stages (one output group only: this loop's scalars took the
+  // kernels of 4 groups from 92 to 96 SGPRs and those of 16 from 64 to 66
+  // VGPRs, either way from 8 waves per SIMD to 7).  Each stage call below is an
+  // if / else pair on tile_nan: the shared with_flag helper in its place moved
+  // all twelve instantiations' code and cost <float, 16, false, 2> a VGPR and
+  // a wave per SIMD.
   if constexpr (kDmaKernel) {
     // The same stages from two LDS buffers filled by LDS-DMA, one barrier a
     // stage.  Stage s sits in buffer (s + 1) & 1: stage 0 went into the second
@@ -1512,9 +1411,7 @@ __global__ void __launch_bounds__(512) bheap_fix_kernel(const KArgs a) {
              !one(std::integral_constant<uint32_t, kFixStage>{})) {
       }
     }
-  } else
-#endif
-  if (KMAX == 1 && 2 * S <= T && forest_bytes <= 0x7fffffff) {
+  } else if (KMAX == 1 && 2 * S <= T && forest_bytes <= 0x7fffffff) {
     // the stages that a full stage follows: everything in range, nothing
     // clamped or guarded.  The forest is read through a buffer resource: a
     // lane's part of a stage is at its constant offset 16 tid, the stage at
@@ -1541,13 +1438,10 @@ __global__ void __launch_bounds__(512) bheap_fix_kernel(const KArgs a) {
       cur = nxt;
     }
   }
-#endif
   for (; t0 < T; t0 += S) {
     const int cnt = (T - t0) < S ? (T - t0) : S;
     __syncthreads();
-#if TI_FIX_SROOT
     fix_tops<NG>(a, t0, top);
-#endif
 #pragma unroll
     for (int u = 0; u < NG; ++u) stage[tid + u * R] = pf[u];
     __syncthreads();
@@ -1771,10 +1665,6 @@ __device__ __forceinline__ uint16_t lds_rxbin(uint32_t byte_addr) {
 // (zero-missing forests) b2 = 2 b + (x == 0) and NaN = 0xFFFE.  Returns
 // (uniformly) whether the tile needs the slow step: a NaN, or with ZB an
 // exact 0.
-#ifndef TI_RX_POSTSTEP
-#define TI_RX_POSTSTEP 1   // layout 6: the group's loop test reads the lanes after the
-                           // step, so no pass runs once every lane is at its leaf
-#endif
 #ifndef TI_RX_BINQ
 #define TI_RX_BINQ 8   // features searched at once per lane (independent load chains;
                        // 16 measured slower on C3 and C4)
@@ -1984,9 +1874,6 @@ __device__ __forceinline__ void rx_leaves(const KArgs& a, ACC (&acc)[KMAX], int 
   }
 }
 
-#ifndef TI_RX_ADDR2
-#define TI_RX_ADDR2 1
-#endif
 // The bin address of a record step (layouts 6-9): (x & mask) | lane offset
 // inside a tree, the lane's own column of word 0 at its leaf.  The empty asm keeps the
 // compiler from rewriting the select as and / cndmask / or: v_and_or_b32 and
@@ -1994,9 +1881,7 @@ __device__ __forceinline__ void rx_leaves(const KArgs& a, ACC (&acc)[KMAX], int 
 template <bool B8 = false>
 __device__ __forceinline__ uint32_t rx_bin_addr(uint32_t x, bool in, uint32_t lane_off) {
   uint32_t t = (x & RxBins<B8>::kOffMask) | lane_off;
-#if TI_RX_ADDR2
   asm("" : "+v"(t));
-#endif
   return in ? t : lane_off;
 }
 
@@ -2006,7 +1891,6 @@ template <bool ZERO, bool SLOW, int ILP>
 __device__ __forceinline__ void rx_descend(const rx_rsrc_t rsrc, const uint32_t (&sb)[ILP],
                                            const uint32_t (&ni)[ILP], uint32_t (&slot)[ILP],
                                            rx_u2_t (&rec)[ILP], uint32_t lane_off) {
-#if TI_RX_POSTSTEP
   bool in[ILP];
   bool any = false;
 #pragma unroll
@@ -2031,29 +1915,6 @@ __device__ __forceinline__ void rx_descend(const rx_rsrc_t rsrc, const uint32_t 
       any |= in[q];
     }
   }
-#else
-  for (;;) {
-    bool in[ILP];
-    uint32_t b[ILP];
-    bool any = false;
-#pragma unroll
-    for (int q = 0; q < ILP; ++q) {
-      in[q] = slot[q] < ni[q];
-      any |= in[q];
-      // a lane at its leaf reads its own column of word 0 (conflict-free)
-      b[q] = lds_u16(rx_bin_addr(rec[q].x, in[q], lane_off));
-    }
-#pragma unroll
-    for (int q = 0; q < ILP; ++q) {
-      const uint32_t nx = rx_next<ZERO, SLOW>(rec[q].x, rec[q].y, (uint16_t)b[q]);
-      if (in[q]) {
-        slot[q] = nx;
-        rec[q] = rx_struct_load(rsrc, nx, 0u, sb[q], 0);
-      }
-    }
-    if (__ballot(any) == 0) break;   // every lane of every tree was at a leaf
-  }
-#endif
 }
 
 template <typename ACC, int KMAX, bool ZERO, bool SLOW, bool VIS, int ILP>

@@ -1,6 +1,6 @@
-"""The fixed walk's rotated 4-tree group (treeinfer_kernels.h bheap_fix_stage,
-TI_FIX_ROT: a tree's step is followed by its own next level's reads, the four
-trees of a group one step apart), bit for bit against the oracle's C port
+"""The fixed walk's rotated 4-tree group (treeinfer_kernels.h bheap_fix_stage:
+a tree's step is followed by its own next level's reads, the four trees of a
+group one step apart), bit for bit against the oracle's C port
 (oracle.port.xgb_predict, margins).
 
 The rotation changes the order of a group's instructions in every stage form
@@ -10,8 +10,8 @@ NaN check -- so the forests sit at the stage edges: depth 8, 28 features, of
 one, two and three peeled stages; and a short last stage of 1 tree behind
 each, whose clamped trees walk but must not be added).  One output group (the
 peeled loop) and three (the multiclass kernels), u16 and u8 bins, the stage of
-8 trees (TI_BHEAP_NG=2) for two of the forests.  Rows are those of
-tests/test_gpu_fix_floor.py: every threshold with one ulp either side and the
+8 trees (TI_BHEAP_NG=2) for two of the forests.  Rows are
+tests/fix_walk_cases.py's: every threshold with one ulp either side and the
 specials; 1,025 of them, so tile 0 holds no NaN, tile 1 does and tile 2 is one
 row; and 1, 63 and 65 rows (less than a wave, a wave and a lane).  float64 X
 goes to the library as it is (it takes the indexed walk) and must give the
@@ -21,71 +21,12 @@ compute unit, each reusing its stage area across ten stages.
 import numpy as np
 import pytest
 
-from kfserving_amd.engine import TI_F64, DeviceForest, _check, _ptr
-from kfserving_amd.forest import OUT_MARGIN
-from kfserving_amd.formats import xgboost_format as xf
-from oracle import port
-from tests.test_gpu_fix_floor import _probe_rows
+from tests import fix_walk_cases as cases
+from tests.fix_walk_cases import ROWS, F
 
 pytestmark = pytest.mark.gpu
 
-BHEAP = 3
-F = 28
 COUNTS = [1, 3, 4, 5, 8, 9, 12, 13, 16, 17]
-ROWS = 1025
-
-_cache = {}
-
-
-def _pool(bits, n=17, seed=191):
-    """n depth-8 trees and their probe rows.  u16 bins: every node of tree 0
-    tests feature 0, so any prefix of the pool has 255 thresholds (> 253) on
-    it.  u8 bins: thresholds on the 253 bounds of max_bin = 254."""
-    key = (bits, n, seed)
-    if key not in _cache:
-        trees, _ = xf.synthetic_complete_trees(n, 8, F, seed=seed, max_bin=0 if bits == 16 else 254)
-        if bits == 16:
-            n_int = int((trees[0]["cleft"] >= 0).sum())
-            trees[0]["sindex"][:n_int] &= np.uint32(0x80000000)   # feature 0, default-left kept
-        # (every 2nd threshold and more of a u16 pool, so the probes fit 1,025 rows)
-        X = _probe_rows(trees, seed=seed + bits, every=1 if bits == 8 else max(2, n // 8))
-        assert X.shape[0] == ROWS and not np.isnan(X[:512]).any() and np.isnan(X[512:1024]).any()
-        _cache[key] = (trees, X)
-    return _cache[key]
-
-
-def _forest(trees, groups):
-    ti = (np.arange(len(trees)) % groups).astype(np.int32)
-    if groups == 1:
-        return ti, xf.forest_from_raw_trees(trees, ti, F, 0, 0.0, "binary:logistic")
-    return ti, xf.forest_from_raw_trees(trees, ti, F, groups, 0.0, "multi:softprob")
-
-
-def _predict_f64(dev, X, groups):
-    """Margins of float64 rows handed to the library as float64."""
-    X = np.ascontiguousarray(X, dtype=np.float64)
-    rows, cols = X.shape
-    out = np.empty(rows * groups, dtype=dev.forest.output_dtype(OUT_MARGIN))
-    _check(dev._lib, dev._lib.ti_predict(dev._handle, _ptr(X), TI_F64, rows, cols, cols, OUT_MARGIN,
-                                         _ptr(out), out.shape[0]))
-    return out
-
-
-def _check_forest(trees, groups, X, bits, row_counts, f64=False):
-    ti, forest = _forest(trees, groups)
-    want = port.xgb_predict(trees, ti, groups, 0.0, F, X)
-    dev = DeviceForest(forest, [0])
-    try:
-        inf = dev.info()
-        assert inf["layout"] == BHEAP and inf["walk"] == 2 and inf["bin_bits"] == bits, inf
-        for rows in row_counts:
-            got = np.asarray(dev.predict(X[:rows], OUT_MARGIN)).reshape(rows, groups)
-            assert np.array_equal(got, want[:rows]), (len(trees), groups, rows)
-            if f64:
-                got = _predict_f64(dev, X[:rows], groups).reshape(rows, groups)
-                assert np.array_equal(got, want[:rows]), (len(trees), groups, rows, "f64")
-    finally:
-        dev.close()
 
 
 @pytest.mark.parametrize("groups", [1, 3])
@@ -94,8 +35,8 @@ def _check_forest(trees, groups, X, bits, row_counts, f64=False):
 def test_tree_counts(n_trees, bits, groups):
     """Every stage count and both forms of the last stage, NaN-free and NaN
     tiles in one launch; float64 X beside float32 at the two ends."""
-    trees, X = _pool(bits)
-    _check_forest(trees[:n_trees], groups, X[:ROWS], bits, [ROWS], f64=n_trees in (1, 17))
+    trees, X = cases.pool(bits)
+    cases.check(trees[:n_trees], groups, X[:ROWS], bits, [ROWS], f64=n_trees in (1, 17))
 
 
 @pytest.mark.parametrize("groups", [1, 3])
@@ -103,8 +44,8 @@ def test_tree_counts(n_trees, bits, groups):
 def test_row_counts(bits, groups):
     """Partial tiles: 1, 63 and 65 rows (the clamped lanes walk too), the
     last two with the NaN of row 600 at their row 40."""
-    trees, X = _pool(bits)
-    _check_forest(trees, groups, X[560:], bits, [1, 63, 65], f64=True)
+    trees, X = cases.pool(bits)
+    cases.check(trees, groups, X[560:], bits, [1, 63, 65], f64=True)
 
 
 @pytest.mark.parametrize("groups", [1, 3])
@@ -115,15 +56,15 @@ def test_stage_of_eight_trees(n_trees, bits, groups, monkeypatch):
     trees, one peeled stage and two guarded ones for 17)."""
     monkeypatch.setenv("TI_DEV_KNOBS", "1")
     monkeypatch.setenv("TI_BHEAP_NG", "2")
-    trees, X = _pool(bits)
-    _check_forest(trees[:n_trees], groups, X[:ROWS], bits, [ROWS])
+    trees, X = cases.pool(bits)
+    cases.check(trees[:n_trees], groups, X[:ROWS], bits, [ROWS])
 
 
 def test_across_tiles():
     """40 trees x 3,000 rows: six workgroups, several on one compute unit, ten
     stages through each one's stage area."""
-    trees, X = _pool(16, n=40, seed=192)
+    trees, X = cases.pool(16, n=40, seed=192)
     rng = np.random.default_rng(5)
     X = np.concatenate([X[:ROWS], rng.standard_normal((3000 - ROWS, F)).astype(np.float32)])
     X[2900, 7] = np.nan
-    _check_forest(trees, 1, X, 16, [3000])
+    cases.check(trees, 1, X, 16, [3000])
