@@ -80,7 +80,8 @@
  *   constant tree inside a linear forest has empty ranges and lin_const =
  *   leaf_value.  Needs leaf_width == 1, accum_dtype == TI_F64, at most 16
  *   output groups, and leaf_id = 0 .. L-1 within each tree (LightGBM's).
- *   TI_OUTPUT_CONTRIB of a linear forest is TI_ERR_UNSUPPORTED (fatal upstream).
+ *   TI_OUTPUT_CONTRIB of a linear forest is TI_ERR_UNSUPPORTED (fatal upstream),
+ *   and so is TI_OUTPUT_INTERACT.
  */
 #ifndef TREEINFER_H_
 #define TREEINFER_H_
@@ -91,7 +92,7 @@
 extern "C" {
 #endif
 
-#define TI_ABI_VERSION 6
+#define TI_ABI_VERSION 7
 
 /* return codes */
 #define TI_OK               0
@@ -131,6 +132,24 @@ extern "C" {
                               /* per group F feature columns, then the bias     */
                               /* (xgboost pred_contribs); needs desc.cover, no  */
                               /* TI_NODE_CAT_XGB node and no linear leaves      */
+#define TI_OUTPUT_INTERACT 4  /* ABI 7: SHAP interaction values (xgboost        */
+                              /* pred_interactions), [rows, K, F + 1, F + 1] in */
+                              /* the accumulator type.  Entry [j][i], i != j, is */
+                              /* half the difference of feature i's contribution */
+                              /* with feature j conditioned on and off; the      */
+                              /* diagonal [j][j] is feature j's contribution     */
+                              /* minus the rest of its row, so a row sums to the */
+                              /* TI_OUTPUT_CONTRIB column of its feature and the */
+                              /* matrix to the margin; the bias row and column   */
+                              /* are zero except [F][F] = bias.  Symmetric up to */
+                              /* rounding.  TI_ERR_UNSUPPORTED wherever          */
+                              /* TI_OUTPUT_CONTRIB is (no covers, a              */
+                              /* TI_NODE_CAT_XGB node, linear leaves), and for   */
+                              /* F + 1 > 128 or a root-to-leaf path of more than */
+                              /* 32 distinct features: there is no generic       */
+                              /* fallback kernel for interactions.  The host     */
+                              /* pipeline (ti_predict) sizes its row chunks by   */
+                              /* this kind's output row, K * (F + 1)^2 elements. */
 
 /*
  * Canonical forest: host structure-of-arrays over the nodes of all trees,
@@ -176,7 +195,8 @@ typedef struct ti_forest_desc {
    * Contributions cover numerical splits and categorical splits with
    * LightGBM's rule (the hot child is the one the rule above picks, as
    * Tree::TreeSHAP does through Decision); a forest with a TI_NODE_CAT_XGB
-   * node or with linear leaves is TI_ERR_UNSUPPORTED for TI_OUTPUT_CONTRIB. */
+   * node or with linear leaves is TI_ERR_UNSUPPORTED for TI_OUTPUT_CONTRIB.
+   * TI_OUTPUT_INTERACT (ABI 7) needs the covers too and is refused alike. */
   const double*  cover;       /* [N]                                                */
   /* linear leaves (ABI 6); NULL / 0 when the forest has none.  CSR over the
    * nodes, internal nodes own empty ranges.  Replaces leaf_const / leaf_features

@@ -46,6 +46,11 @@ void free_device(DeviceForest& d) {
   static_cast<ForestPtrs&>(d) = ForestPtrs();
   free_shap(d);
   free_scratch(d);
+  if (d.interact_done) (void)hipEventDestroy(d.interact_done);
+  if (d.interact_buf) (void)hipFree(d.interact_buf);
+  d.interact_done = nullptr;
+  d.interact_buf = nullptr;
+  d.interact_cap = 0;
   if (d.stream) (void)hipStreamDestroy(d.stream);
   d.stream = nullptr;
   d.device = -1;
@@ -174,6 +179,7 @@ void occ_note(KernelFn fn, int block, size_t lds) {
 int64_t output_width(const ti_forest* f, int kind) {
   if (kind == TI_OUTPUT_LEAF) return f->T;
   if (kind == TI_OUTPUT_CONTRIB) return static_cast<int64_t>(f->K) * (f->F + 1);
+  if (kind == TI_OUTPUT_INTERACT) return static_cast<int64_t>(f->K) * (f->F + 1) * (f->F + 1);
   if (kind == TI_OUTPUT_PREDICT && f->transform == TI_TRANSFORM_ARGMAX) return 1;
   return f->K;
 }
@@ -498,6 +504,21 @@ int64_t chunk_rows(size_t row_bytes) {
   return r;
 }
 
+// The chunk of one call.  Every kind but TI_OUTPUT_INTERACT sizes it by the
+// input row, as above.  An interaction row is K * (F + 1)^2 outputs, far
+// wider than its input (C2: 3,364 B against 112 B), and the lanes hold a
+// chunk of output as well: there TI_CHUNK_MB bounds the wider of the two
+// rows, in whole 64-row waves (the interaction kernels have no 512-row tile).
+int64_t chunk_rows_for(const ti_forest* f, int xdt, int64_t stride, int kind) {
+  const size_t x_row = static_cast<size_t>(stride) * dtype_size(xdt);
+  if (kind != TI_OUTPUT_INTERACT) return chunk_rows(x_row);
+  const size_t o_row = dtype_size(output_dtype(f, kind)) * static_cast<size_t>(output_width(f, kind));
+  const int mb = env_int("TI_CHUNK_MB", 64);
+  const int64_t r = static_cast<int64_t>((static_cast<size_t>(std::max(mb, 1)) << 20) /
+                                         std::max<size_t>(std::max(x_row, o_row), 1));
+  return std::max<int64_t>(64, r & ~int64_t(63));
+}
+
 // Batches larger than one chunk: chunks alternate between two lanes (streams
 // with their own pinned and device buffers).  While lane A runs chunk c
 // (H2D -> kernel -> D2H), the host copies chunk c+1 into lane B's pinned
@@ -676,7 +697,7 @@ int predict_shard(ti_forest* f, int slot, DeviceForest& d, const unsigned char* 
   std::lock_guard<std::mutex> lk(d.mu);
   TI_HIP(hipSetDevice(d.device));
   {
-    const int64_t ch = chunk_rows(static_cast<size_t>(stride) * dtype_size(xdt));
+    const int64_t ch = chunk_rows_for(f, xdt, stride, kind);
     if (rows > ch) {
       if (reg) {
         const int rc = predict_registered(f, slot, d, X, xdt, rows, cols, stride, kind, out, ch,
@@ -775,6 +796,21 @@ int launch_chunked(ti_forest* f, int slot, const void* X, int xdt, int64_t rows,
   int32_t* dmap = nullptr;
   int rc = TI_OK;
   size_t tmp_bytes = 0;
+  if (kind == TI_OUTPUT_INTERACT) {
+    // (F + 1)^2 columns a group.  A part's finishing kernel writes its groups'
+    // matrices straight into their columns of the [rows, K, F + 1, F + 1]
+    // output (row pitch = the whole forest's row): the largest output there is
+    // gets no scratch copy and no second pass over it.
+    const int64_t cw = static_cast<int64_t>(f->F + 1) * (f->F + 1);
+    for (size_t c = 0; c < f->parts.size(); ++c) {
+      ti_forest* p = f->parts[c].get();
+      const int rc = launch_interact(p, *p->devs[slot], X, xdt, rows, cols, stride,
+                                     static_cast<unsigned char*>(out) + f->part_k0[c] * cw * as,
+                                     f->K * cw, stream);
+      if (rc) return rc;
+    }
+    return TI_OK;
+  }
   const int64_t cw = kind == TI_OUTPUT_CONTRIB ? f->F + 1 : 1;   // columns per group
   for (auto& p : f->parts)
     tmp_bytes = std::max(tmp_bytes, static_cast<size_t>(rows) *
@@ -894,8 +930,15 @@ int launch_any(ti_forest* f, int slot, const void* X, int xdt, int64_t rows, int
     return fail(TI_ERR_UNSUPPORTED,
                 "TI_OUTPUT_CONTRIB of a forest with linear leaves (LightGBM itself refuses "
                 "pred_contrib on a linear-tree model)");
+  if (kind == TI_OUTPUT_INTERACT && f->linear)
+    return fail(TI_ERR_UNSUPPORTED,
+                "TI_OUTPUT_INTERACT of a forest with linear leaves (contributions of a linear-tree "
+                "model are refused too)");
   if (kind == TI_OUTPUT_CONTRIB && f->parts.empty())
     return launch_contrib(f, *f->devs[slot], X, xdt, rows, cols, stride, out, stream);
+  if (kind == TI_OUTPUT_INTERACT && f->parts.empty())
+    return launch_interact(f, *f->devs[slot], X, xdt, rows, cols, stride, out,
+                           output_width(f, kind), stream);
   if (!f->parts.empty())
     return launch_chunked(f, slot, X, xdt, rows, cols, stride, kind, out, stream);
   if (f->linear && (kind == TI_OUTPUT_MARGIN || kind == TI_OUTPUT_PREDICT))
@@ -1120,7 +1163,7 @@ int ti_forest_set_option(ti_forest* f, int32_t option, int64_t value) {
 int ti_output_shape(const ti_forest* f, int32_t kind, int64_t n_rows, int64_t* out_len,
                     int32_t* out_dtype) {
   if (!f || !out_len || !out_dtype) return fail(TI_ERR_INVALID, "null argument");
-  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_CONTRIB) return fail(TI_ERR_INVALID, "bad output kind");
+  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_INTERACT) return fail(TI_ERR_INVALID, "bad output kind");
   if (n_rows < 0) return fail(TI_ERR_INVALID, "negative n_rows");
   *out_len = n_rows * output_width(f, kind);
   *out_dtype = output_dtype(f, kind);
@@ -1131,7 +1174,7 @@ static int check_call(const ti_forest* f, const void* X, int32_t xdt, int64_t ro
                       int64_t stride, int32_t kind, const void* out, int64_t out_len) {
   if (!f) return fail(TI_ERR_INVALID, "null forest");
   if (xdt != TI_F32 && xdt != TI_F64) return fail(TI_ERR_INVALID, "x_dtype must be TI_F32 or TI_F64");
-  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_CONTRIB) return fail(TI_ERR_INVALID, "bad output kind");
+  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_INTERACT) return fail(TI_ERR_INVALID, "bad output kind");
   if (rows < 0) return fail(TI_ERR_INVALID, "negative n_rows");
   if (rows == 0) return TI_OK;
   if (!X || !out) return fail(TI_ERR_INVALID, "null data pointer");
@@ -1165,7 +1208,7 @@ int ti_predict(ti_forest* f, const void* X, int32_t xdt, int64_t rows, int32_t c
   // be registered every shard takes the pinned staging chunks.
   HostSpan all_x, all_o;
   int reg_mode = 0;
-  if (hreg && per > chunk_rows(static_cast<size_t>(stride) * xs)) {
+  if (hreg && per > chunk_rows_for(f, xdt, stride, kind)) {
     const size_t x_bytes = static_cast<size_t>((rows - 1) * stride + cols) * xs;
     if (all_x.reg(xb, x_bytes, true) && all_o.reg(ob, static_cast<size_t>(rows) * os, true))
       reg_mode = 2;

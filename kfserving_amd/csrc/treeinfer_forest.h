@@ -301,6 +301,13 @@ struct DeviceForest : ForestPtrs, ShapPtrs, ScratchBufs {
   DeviceAllocs forest_mem, shap_mem;
   std::atomic<int32_t> shap_tab_state{0};   // 0 not tried, 1 built, -1 failed or over the cap:
                                      // contributions use the extend / unwind kernel
+  // TI_OUTPUT_INTERACT scratch (launch_interact: contributions + partials of
+  // one call): grow-only device memory of the replica's own, handed from one
+  // call to the next, whatever their streams, through interact_done
+  std::mutex interact_mu;
+  void* interact_buf = nullptr;
+  size_t interact_cap = 0;
+  hipEvent_t interact_done = nullptr;
   int64_t bytes = 0;
   std::mutex mu;
 };

@@ -433,9 +433,182 @@ __global__ void __launch_bounds__(256) contrib_slices_kernel(
   }
 }
 
+// SHAP interaction values (TI_OUTPUT_INTERACT), the off-diagonal part.  For a
+// path with merged elements 0..n-1 (one fraction o_i = bit i of om, zero
+// fraction z_i, leaf value v), conditioning on element j takes j out of the
+// path and scales the leaf by o_j (on) or z_j (off), so for i != j
+//   Phi[feat_j][feat_i] += 1/2 (o_j - z_j) (o_i - z_i) UnwoundPathSum_i(w^-j) v
+// with w^-j the path weights of the n - 1 other elements (xgboost's TreeShap
+// with condition = +-1, PredictInteractionContributions).
+//
+// One row per lane, path slices on blockIdx.y, as contrib_reg_kernel.
+// blockIdx.z = g * nb + b names an output group g and a block of cpb =
+// kShapLdsW / (F + 1) conditioned features [j0, j1); the block's accumulators
+// [(j1 - j0) * (F + 1)][64] of MT are the LDS budget of contrib_reg_kernel.
+// A path of another group (scalar leaves), of fewer than two elements or with
+// no element in [j0, j1) is skipped under a scalar branch before any row is
+// read.
+//
+// w^-j is extended from scratch over the elements other than j, not unwound
+// from the full weights: the unwind divides by z_j where o_j = 0 and by o_j's
+// chain where it is 1, which branches per lane and amplifies float32 error
+// for small z_j; the extension is the arithmetic xgboost itself does under a
+// condition, is uniform across the wave (j is a scalar), and costs
+// n^2 / 2 multiply-adds beside the n^2 of the n - 1 unwound sums that follow
+// either way.  The full weights w[0..n] are then never needed: the diagonal
+// comes from the contributions (interact_finish_kernel).
+//
+// Raw partials go to part[slice][(g * F + feat_j) * (F + 1) + feat_i][rows];
+// nothing is read back, no atomics.  The output type plays no part here, so
+// the kernel is not instantiated per ACC.
+template <typename XT, typename MT, int MAXN>
+__global__ void __launch_bounds__(64) interact_reg_kernel(
+    const XT* __restrict__ X, int64_t rows, int64_t stride, int32_t cols, int32_t zero_map_on,
+    const ShapPath* __restrict__ paths, int64_t n_paths, const ShapElem* __restrict__ elems,
+    const double* __restrict__ leafv, int32_t LW, int32_t K, int32_t F, int32_t cpb, int32_t nb,
+    double* __restrict__ part, int64_t paths_per_slice, const ShapCatRef* __restrict__ cat_refs,
+    const uint32_t* __restrict__ cat_words) {
+  extern __shared__ double shap_lds[];
+  const int lane = threadIdx.x;
+  const int64_t row = (int64_t)blockIdx.x * 64 + lane;
+  const bool live = row < rows;
+  const XT* xr = X + (live ? row : rows - 1) * stride;
+  const int F1 = F + 1;
+  const int g = (int)blockIdx.z / nb;
+  const int j0 = ((int)blockIdx.z - g * nb) * cpb;
+  const int j1 = j0 + cpb < F ? j0 + cpb : F;
+  const int C = (j1 - j0) * F1;
+  MT* acc = reinterpret_cast<MT*>(shap_lds) + lane;   // acc[c * 64]
+  for (int c = 0; c < C; ++c) acc[c * 64] = MT(0);
+  const int64_t p_begin = (int64_t)blockIdx.y * paths_per_slice;
+  const int64_t p_end = p_begin + paths_per_slice < n_paths ? p_begin + paths_per_slice : n_paths;
+  for (int64_t p = p_begin; p < p_end; ++p) {
+    const ShapPath P = paths[p];
+    const int n = P.n;
+    if (n < 2 || (LW == 1 && P.group != g)) continue;
+    const ShapElem* pe = elems + P.first;
+    bool mine = false;
+    for (int i = 0; i < n; ++i) {
+      const int32_t fe = pe[i].feature;
+      mine = mine || (fe >= j0 && fe < j1);
+    }
+    if (!mine) continue;
+    uint32_t om = 0u;                             // one fractions, bit i = element i
+    for (int i = 0; i < n; ++i) {
+      const ShapElem e = pe[i];
+      double x = e.feature < cols ? (double)xr[e.feature] : __builtin_nan("");
+      if (zero_map_on && __builtin_fabs(x) <= (double)1e-35f) x = 0.0;
+      om |= (shap_follow_num(e, x) ? 1u : 0u) << i;
+    }
+    if (cat_refs) {
+      for (int i = 0; i < n; ++i) {
+        const int32_t fe = pe[i].feature;
+        const uint32_t fl = pe[i].flags;
+        if (!(fl & kShapCat)) continue;
+        const double x = fe < cols ? (double)xr[fe] : __builtin_nan("");
+        if (!shap_follow_cat(fl, x, P.first + i, cat_refs, cat_words)) om &= ~(1u << i);
+      }
+    }
+    const MT lv = static_cast<MT>(leafv[P.leaf * LW + (LW == 1 ? 0 : g)]);
+    const int m = n - 1;                          // elements of the conditioned path
+    const MT rm1 = static_cast<MT>(m + 1);
+    const MT im1 = static_cast<MT>(kShapInv.v[m + 1]);
+    for (int j = 0; j < n; ++j) {
+      const int32_t fj = pe[j].feature;
+      if (fj < j0 || fj >= j1) continue;
+      // ExtendPath over the elements other than j
+      MT w[MAXN];
+      w[0] = MT(1);
+#pragma unroll
+      for (int d = 1; d < MAXN; ++d) {
+        if (d <= m) {
+          const int src = d - 1 + (d - 1 >= j ? 1 : 0);
+          const MT of = ((om >> src) & 1u) ? MT(1) : MT(0);
+          const MT zf = static_cast<MT>(pe[src].zf);
+          w[d] = MT(0);
+#pragma unroll
+          for (int i = d - 1; i >= 0; --i) {
+            w[i + 1] += of * w[i] * static_cast<MT>((double)(i + 1) / (double)(d + 1));
+            w[i] = zf * w[i] * static_cast<MT>((double)(d - i) / (double)(d + 1));
+          }
+        }
+      }
+      MT wm = MT(0);                              // w[m]
+#pragma unroll
+      for (int i = 0; i < MAXN; ++i)
+        if (i == m) wm = w[i];
+      const MT oj = ((om >> j) & 1u) ? MT(1) : MT(0);
+      const MT cj = MT(0.5) * (oj - static_cast<MT>(pe[j].zf)) * lv;
+      MT* accj = acc + (fj - j0) * F1 * 64;
+      for (int e_i = 0; e_i < n; ++e_i) {
+        if (e_i == j) continue;
+        // UnwoundPathSum of element e_i in w^-j: both branches, selected per
+        // lane (the branch on `one` diverges within a wave anyway)
+        const bool one = ((om >> e_i) & 1u) != 0u;
+        const MT zf = static_cast<MT>(pe[e_i].zf);
+        const MT izf = MT(1) / zf;
+        MT next = wm, tot1 = MT(0), tot0 = MT(0);
+#pragma unroll
+        for (int i = MAXN - 2; i >= 0; --i) {
+          if (i < m) {
+            const MT tmp = next * (rm1 * static_cast<MT>(1.0 / (double)(i + 1)));
+            tot1 += tmp;
+            next = w[i] - tmp * zf * (static_cast<MT>(m - i) * im1);
+            tot0 += w[i] * izf * (rm1 * static_cast<MT>(kShapInv.v[m - i]));
+          }
+        }
+        const MT s = (one ? tot1 : tot0) * ((one ? MT(1) : MT(0)) - zf);
+        accj[pe[e_i].feature * 64] += cj * s;
+      }
+    }
+  }
+  if (!live) return;
+  const int64_t W2 = (int64_t)K * F * F1;
+  double* pp = part + ((int64_t)blockIdx.y * W2 + (int64_t)(g * F + j0) * F1) * rows + row;
+  for (int c = 0; c < C; ++c) pp[(int64_t)c * rows] = static_cast<double>(acc[c * 64]);
+}
+
+// One thread per (row, group, matrix row fj): the off-diagonal entries are
+// the path slices' partials summed in slice order in float64 over the
+// divisor; the diagonal is the feature's contribution (phi, launch_contrib's
+// output) minus the off-diagonal entries as written, so a row of the matrix
+// sums to the contribution; the bias row and column are zero but for
+// Phi[F][F] = bias (xgboost's PredictInteractionContributions).
+template <typename ACC>
+__global__ void __launch_bounds__(64) interact_finish_kernel(
+    const double* __restrict__ part, int32_t slices, int64_t rows, int32_t K, int32_t F,
+    const ACC* __restrict__ phi, const double* __restrict__ bias, double divisor,
+    ACC* __restrict__ out, int64_t out_ld) {
+  const int64_t row = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (row >= rows) return;
+  const int F1 = F + 1;
+  const int g = (int)blockIdx.y / F1;
+  const int fj = (int)blockIdx.y - g * F1;
+  ACC* o = out + row * out_ld + (int64_t)blockIdx.y * F1;   // out_ld: elements an output row
+  if (fj == F) {
+    for (int fi = 0; fi < F; ++fi) o[fi] = ACC(0);
+    o[F] = (ACC)bias[g];
+    return;
+  }
+  const int64_t W2 = (int64_t)K * F * F1;
+  const int64_t c0 = (int64_t)(g * F + fj) * F1;
+  double off = 0.0;
+  for (int fi = 0; fi < F; ++fi) {
+    if (fi == fj) continue;
+    double t = 0.0;
+    for (int sl = 0; sl < slices; ++sl) t += part[((int64_t)sl * W2 + c0 + fi) * rows + row];
+    const ACC v = (ACC)(t / divisor);
+    o[fi] = v;
+    off += static_cast<double>(v);
+  }
+  o[fj] = (ACC)(static_cast<double>(phi[row * K * F1 + blockIdx.y]) - off);
+  o[F] = ACC(0);
+}
+
 namespace {
 
 int ensure_lds_attr(int device, KernelFn fn);   // treeinfer.hip
+void occ_note(KernelFn fn, int block, size_t lds);
 
 // the TreeSHAP buffers of one replica (device current), after a failed upload
 // or with the replica; the caller restores `bytes`
@@ -755,8 +928,11 @@ void ensure_shap_table(ti_forest* f, DeviceForest& d) {
       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
+// use_table = false keeps a call on the extend / unwind arithmetic whatever
+// the batch size (launch_interact: see there).
 int launch_contrib(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows,
-                   int32_t cols, int64_t stride, void* out, hipStream_t stream) {
+                   int32_t cols, int64_t stride, void* out, hipStream_t stream,
+                   bool use_table = true) {
   if (!f->has_shap)
     return fail(TI_ERR_UNSUPPORTED,
                 f->shap_refused == 2
@@ -793,7 +969,7 @@ int launch_contrib(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_
     // 4.1e5 vs 2.7e5 rows/s); at 100k rows its gathers (a 64-row wave reads
     // most of each path's 2^n x 32 B block) make it slower than the extend /
     // unwind arithmetic (2.2e5 vs 2.9e5): profiles/r3_shap_table.jsonl
-    const bool want_tab = f->shap_tab_mt != 0 && rows <= f->shap_tab_rows;
+    const bool want_tab = use_table && f->shap_tab_mt != 0 && rows <= f->shap_tab_rows;
     if (want_tab && d.shap_tab_state == 0) ensure_shap_table(f, d);
     double* part = nullptr;
     if (slices > 1)
@@ -904,6 +1080,161 @@ int launch_contrib(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_
   TI_HIP(hipGetLastError());
   if (acc != out) TI_HIP(hipFreeAsync(acc, stream));
   return TI_OK;
+}
+
+// TI_OUTPUT_INTERACT on one (unchunked) forest: [rows, K, F + 1, F + 1].  The
+// contributions go to a scratch through launch_contrib; interact_reg_kernel
+// writes the off-diagonal partials of one row block and
+// interact_finish_kernel assembles the block's matrices.  A row block is as
+// many 64-row waves as keep one slice of partials within kShapPartBytesMax
+// (path slices are dropped first, as for contributions).  There is no generic
+// kernel: a matrix row wider than kShapLdsW, or a path of more than 32
+// features, is refused.  out_ld is the output's row pitch in elements: K * (F
+// + 1)^2, or the whole forest's row when f is a group part that writes its
+// groups' matrices in place (launch_chunked).
+int launch_interact(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows,
+                    int32_t cols, int64_t stride, void* out, int64_t out_ld, hipStream_t stream) {
+  if (!f->has_shap)
+    return fail(TI_ERR_UNSUPPORTED,
+                f->shap_refused == 2
+                    ? "interactions of categorical splits with XGBoost's rule (TI_NODE_CAT_XGB) are "
+                      "not supported; categorical splits with LightGBM's rule are"
+                    : "interactions need node covers (ti_forest_desc.cover)");
+  {
+    const int rc = ensure_shap(f);
+    if (rc) return rc;
+  }
+  const int F = f->F, F1 = F + 1, K = f->K;
+  if (F1 > kShapLdsW)
+    return fail(TI_ERR_UNSUPPORTED, "interactions need n_features + 1 <= " + std::to_string(kShapLdsW) +
+                                        " (one matrix row of accumulators in LDS); the forest has " +
+                                        std::to_string(F) + " features");
+  if (f->shap_maxl > 32)
+    return fail(TI_ERR_UNSUPPORTED, "interactions need paths of at most 32 unique features; the "
+                                    "forest's longest has " + std::to_string(f->shap_maxl));
+  if (rows == 0) return TI_OK;
+  const size_t as = f->accum == TI_F64 ? 8 : 4;
+  const size_t xs = xdt == TI_F64 ? 8 : 4;
+  const int64_t n_paths = static_cast<int64_t>(d.shap_paths ? 1 : 0) * f->shap_npaths;
+  const int maxn = f->shap_maxl <= 8 ? 8 : f->shap_maxl <= 16 ? 16 : 32;
+  const bool f32_math = f->accum != TI_F64 && !env_int("TI_SHAP_F64", 0);
+  const int cpb = kShapLdsW / F1;                    // conditioned features a block
+  const int nb = F > 0 ? (F + cpb - 1) / cpb : 0;    // blocks a group
+  const size_t lds = static_cast<size_t>(std::min(cpb, std::max(F, 1)) * F1) * 64 * (f32_math ? 4 : 8);
+  const int64_t W2 = static_cast<int64_t>(K) * F * F1;   // partial columns
+  // TI_SHAP_PART_MB (developer knob): the partials' bound, so that a test
+  // reaches the row-block loop without a 2 GiB batch
+  const int part_mb = env_int("TI_SHAP_PART_MB", 0);
+  const uint64_t part_max = part_mb > 0 ? static_cast<uint64_t>(part_mb) << 20 : kShapPartBytesMax;
+  int64_t rb = static_cast<int64_t>(part_max / static_cast<uint64_t>(std::max<int64_t>(W2, 1) * 8));
+  rb = std::min(rows, std::max<int64_t>(64, rb / 64 * 64));
+  const int64_t grid_rb = (rb + 63) / 64;
+  const int64_t waves = grid_rb * std::max(K * nb, 1);
+  const int force_slices = env_int("TI_SHAP_SLICES", 0);
+  // TI_SHAP_SLICES (developer knob) names the count outright, for forests of
+  // any size; otherwise enough slices to fill the device, of at least
+  // kShapMinPathsPerSlice paths each
+  int64_t slices = force_slices > 0
+                       ? std::min<int64_t>(force_slices, std::max<int64_t>(n_paths, 1))
+                       : std::min<int64_t>((kShapWaveTarget + waves - 1) / waves,
+                                           std::max<int64_t>(1, n_paths / kShapMinPathsPerSlice));
+  slices = std::min<int64_t>(slices, kShapMaxSlices);
+  while (slices > 1 && static_cast<uint64_t>(slices) * W2 * rb * 8 > part_max) --slices;
+  slices = std::max<int64_t>(slices, 1);
+  const int64_t pps = (n_paths + slices - 1) / slices;
+  // The call's scratch: the contributions [rows, K * (F + 1)] of the output
+  // type, then the partials of one row block, in the replica's own grow-only
+  // buffer.  Every kernel that writes or reads it is launched below on
+  // `stream`, in order; a later call, on any stream, first waits for
+  // interact_done, which this call records behind its last kernel, and the
+  // buffer grows only after that event has completed.  interact_mu covers
+  // the hand-over (wait, grow, launches, record), not the kernels' run.
+  const size_t phi_bytes = (static_cast<size_t>(rows) * K * F1 * as + 255) & ~size_t(255);
+  const size_t part_bytes = static_cast<size_t>(slices * W2 * rb) * 8;
+  std::lock_guard<std::mutex> scratch_lk(d.interact_mu);
+  if (!d.interact_done) {
+    TI_HIP(hipEventCreateWithFlags(&d.interact_done, hipEventDisableTiming));
+  } else if (phi_bytes + part_bytes > d.interact_cap) {
+    TI_HIP(hipEventSynchronize(d.interact_done));
+  } else {
+    TI_HIP(hipStreamWaitEvent(stream, d.interact_done, 0));
+  }
+  if (phi_bytes + part_bytes > d.interact_cap) {
+    if (d.interact_buf) (void)hipFree(d.interact_buf);
+    d.interact_buf = nullptr;
+    d.interact_cap = 0;
+    const size_t want_cap = std::max<size_t>(phi_bytes + part_bytes, size_t(1) << 20);
+    if (hipMalloc(&d.interact_buf, want_cap) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(TI_ERR_NOMEM, "interaction scratch allocation failed");
+    }
+    d.interact_cap = want_cap;
+  }
+  unsigned char* scratch = static_cast<unsigned char*>(d.interact_buf);
+  void* phi = scratch;
+  double* part = reinterpret_cast<double*>(scratch + phi_bytes);
+  // The contributions by arithmetic, never through the coefficient table: they
+  // are a small share of this call (the interactions are about n times their
+  // work), and a request for matrices then neither builds nor waits for a
+  // table of up to TI_OPT_SHAP_TABLE_MB that contributions requests may never
+  // ask for.
+  int rc = launch_contrib(f, d, X, xdt, rows, cols, stride, phi, stream, false);
+  if (rc) {
+    (void)hipEventRecord(d.interact_done, stream);
+    return rc;
+  }
+#define TI_INTERACT(XT_, MT_, N_)                                                                 \
+  do {                                                                                            \
+    KernelFn fn_ = reinterpret_cast<KernelFn>(interact_reg_kernel<XT_, MT_, N_>);                 \
+    rc = ensure_lds_attr(d.device, fn_);                                                          \
+    if (rc == TI_OK) {                                                                            \
+      occ_note(fn_, 64, lds);                                                                     \
+      hipLaunchKernelGGL((interact_reg_kernel<XT_, MT_, N_>),                                     \
+                         dim3(grid_r, (unsigned)slices, (unsigned)(K * nb)), dim3(64), lds, stream, \
+                         static_cast<const XT_*>(xb), n, stride, cols, f->lgb_zero_map,           \
+                         d.shap_paths, n_paths, d.shap_elems, d.shap_leaf, f->LW, K, F, cpb, nb,  \
+                         part, pps, d.shap_cat_refs, d.shap_cat_words);                           \
+    }                                                                                             \
+  } while (0)
+#define TI_INTERACT_N(XT_, MT_)                       \
+  do {                                                \
+    if (maxn == 8) TI_INTERACT(XT_, MT_, 8);          \
+    else if (maxn == 16) TI_INTERACT(XT_, MT_, 16);   \
+    else TI_INTERACT(XT_, MT_, 32);                   \
+  } while (0)
+  for (int64_t r0 = 0; r0 < rows && rc == TI_OK; r0 += rb) {
+    const int64_t n = std::min(rb, rows - r0);
+    const unsigned grid_r = static_cast<unsigned>((n + 63) / 64);
+    const void* xb = static_cast<const unsigned char*>(X) + static_cast<size_t>(r0 * stride) * xs;
+    if (nb > 0) {
+      // path arithmetic in the forest's accumulator type, as for contributions
+      if (xdt == TI_F32) {
+        if (f32_math) TI_INTERACT_N(float, float);
+        else TI_INTERACT_N(float, double);
+      } else {
+        if (f32_math) TI_INTERACT_N(double, float);
+        else TI_INTERACT_N(double, double);
+      }
+      if (rc) break;
+    }
+    const dim3 g2(grid_r, static_cast<unsigned>(K * F1));
+    unsigned char* ob = static_cast<unsigned char*>(out) + static_cast<size_t>(r0 * out_ld) * as;
+    const unsigned char* pb = static_cast<const unsigned char*>(phi) + static_cast<size_t>(r0) * K * F1 * as;
+    if (f->accum == TI_F64)
+      hipLaunchKernelGGL((interact_finish_kernel<double>), g2, dim3(64), 0, stream, part,
+                         (int32_t)slices, n, K, F, reinterpret_cast<const double*>(pb), d.shap_bias,
+                         f->divisor, reinterpret_cast<double*>(ob), out_ld);
+    else
+      hipLaunchKernelGGL((interact_finish_kernel<float>), g2, dim3(64), 0, stream, part,
+                         (int32_t)slices, n, K, F, reinterpret_cast<const float*>(pb), d.shap_bias,
+                         f->divisor, reinterpret_cast<float*>(ob), out_ld);
+  }
+#undef TI_INTERACT_N
+#undef TI_INTERACT
+  if (rc == TI_OK && hipGetLastError() != hipSuccess)
+    rc = fail(TI_ERR_DEVICE, "interaction kernel launch failed");
+  (void)hipEventRecord(d.interact_done, stream);   // the next call's scratch waits for this one
+  return rc;
 }
 
 }  // namespace

@@ -45,6 +45,7 @@ OUT_MARGIN = 0
 OUT_PREDICT = 1
 OUT_LEAF = 2
 OUT_CONTRIB = 3     # TreeSHAP contributions [rows, K * (F + 1)], bias last per group
+OUT_INTERACT = 4    # SHAP interaction values [rows, K * (F + 1) * (F + 1)] (pred_interactions)
 
 # LightGBM missing types (decision_type bits 2-3)
 MISSING_NONE = 0
@@ -265,6 +266,8 @@ class Forest:
             return self.n_trees
         if kind == OUT_CONTRIB:
             return self.n_groups * (self.n_features + 1)
+        if kind == OUT_INTERACT:
+            return self.n_groups * (self.n_features + 1) ** 2
         if kind == OUT_PREDICT and self.transform == T_ARGMAX:
             return 1
         return self.n_groups

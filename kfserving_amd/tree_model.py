@@ -15,7 +15,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from .engine import DeviceForest, prepare_input
-from .forest import OUT_CONTRIB, OUT_PREDICT, Forest
+from .forest import OUT_CONTRIB, OUT_INTERACT, OUT_PREDICT, Forest
 
 
 class GPUForestMixin:
@@ -95,10 +95,21 @@ class GPUForestMixin:
         ``predict(pred_contribs=True)``: [rows, F + 1] for one output group,
         [rows, K, F + 1] for K groups; the last column is the bias (base
         margin + expected tree output).  The request is parsed exactly as
-        ``predict`` parses it (``request_matrix``)."""
+        ``predict`` parses it (``request_matrix``).
+
+        A request with top-level ``"pred_interactions": true`` (xgboost's
+        name) gets SHAP interaction values instead (TI_OUTPUT_INTERACT):
+        [rows, F + 1, F + 1], or [rows, K, F + 1, F + 1] for K groups; every
+        row of a matrix sums to the contribution the plain request returns."""
         try:
             X = self.request_matrix(request)
             f = self._forest
+            if isinstance(request, dict) and request.get("pred_interactions") is True:
+                n = f.n_features + 1
+                m = self.predict_matrix(X, OUT_INTERACT)
+                m = m.reshape((m.shape[0], f.n_groups, n, n) if f.n_groups > 1
+                              else (m.shape[0], n, n))
+                return {"explanations": m.tolist()}
             c = self.predict_matrix(X, OUT_CONTRIB)
             if f.n_groups > 1:
                 c = c.reshape(c.shape[0], f.n_groups, f.n_features + 1)

@@ -29,7 +29,7 @@ from typing import Callable, List, Optional, Tuple
 
 import numpy as np
 
-from .forest import OUT_CONTRIB, OUT_LEAF, OUT_MARGIN, OUT_PREDICT, TI_F32, Forest
+from .forest import OUT_CONTRIB, OUT_INTERACT, OUT_LEAF, OUT_MARGIN, OUT_PREDICT, TI_F32, Forest
 
 
 def partition_trees(forest: Forest, world: int) -> List[Tuple[int, int]]:
@@ -93,6 +93,9 @@ class TreeShardedForest:
         same rows).  Returns the full output on the root (PREDICT and LEAF
         shaped as DeviceForest.predict returns them, MARGIN [rows, K], CONTRIB
         [rows, K * (F + 1)]) and None elsewhere."""
+        if kind == OUT_INTERACT:   # it would fall through to the margin path below
+            raise ValueError("kind OUT_INTERACT (SHAP interaction values) is not served "
+                             "tree-sharded; use DeviceForest.predict")
         import torch
         import torch.distributed as dist
         rows, cols = int(X.shape[0]), int(X.shape[1])
