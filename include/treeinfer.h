@@ -92,7 +92,7 @@
 extern "C" {
 #endif
 
-#define TI_ABI_VERSION 7
+#define TI_ABI_VERSION 8
 
 /* return codes */
 #define TI_OK               0
@@ -150,6 +150,32 @@ extern "C" {
                               /* fallback kernel for interactions.  The host     */
                               /* pipeline (ti_predict) sizes its row chunks by   */
                               /* this kind's output row, K * (F + 1)^2 elements. */
+#define TI_OUTPUT_CONTRIB_APPROX 5
+                              /* ABI 8: approximate (Saabas) contributions,      */
+                              /* xgboost approx_contribs: [rows, K * (F + 1)]    */
+                              /* laid out, typed, based and divided exactly as   */
+                              /* TI_OUTPUT_CONTRIB.  Per tree, mean[n] is the    */
+                              /* leaf value at a leaf and (mean[l] * cover[l] +  */
+                              /* mean[r] * cover[r]) / cover[n] elsewhere        */
+                              /* (xgboost FillNodeMeanValues; per entry of a     */
+                              /* vector leaf).  A row that walks root = n0 -> n1 */
+                              /* -> ... -> leaf by the canonical split rule above */
+                              /* (every rule, TI_NODE_CAT_XGB included) adds      */
+                              /* mean[n(i+1)] - mean[n(i)] to column             */
+                              /* feature[n(i)] and mean[root] to the bias column, */
+                              /* in float64; a tree whose root is a leaf adds    */
+                              /* only bias.  The columns of a row sum to the     */
+                              /* margin whatever the covers are (the sum         */
+                              /* telescopes).  A node of zero cover divides by   */
+                              /* it, as the TreeSHAP bias does: its mean and what */
+                              /* is formed from it are NaN or infinite.          */
+                              /* TI_ERR_UNSUPPORTED for a forest without covers, */
+                              /* with linear leaves, or with a tree whose leaf   */
+                              /* ids are negative or not distinct (a leaf's terms */
+                              /* are found by the id TI_OUTPUT_LEAF reports);    */
+                              /* F, K, depth and path length do not restrict it. */
+                              /* The host pipeline sizes its row chunks by this  */
+                              /* kind's output row.                              */
 
 /*
  * Canonical forest: host structure-of-arrays over the nodes of all trees,

@@ -20,6 +20,7 @@
 #include "treeinfer_forest.h"
 #include "treeinfer_pack.h"
 #include "treeinfer_shap.h"
+#include "treeinfer_approx.h"
 
 namespace {
 
@@ -45,6 +46,7 @@ void free_device(DeviceForest& d) {
   d.forest_mem.release();
   static_cast<ForestPtrs&>(d) = ForestPtrs();
   free_shap(d);
+  free_approx(d);
   free_scratch(d);
   if (d.interact_done) (void)hipEventDestroy(d.interact_done);
   if (d.interact_buf) (void)hipFree(d.interact_buf);
@@ -178,7 +180,8 @@ void occ_note(KernelFn fn, int block, size_t lds) {
 
 int64_t output_width(const ti_forest* f, int kind) {
   if (kind == TI_OUTPUT_LEAF) return f->T;
-  if (kind == TI_OUTPUT_CONTRIB) return static_cast<int64_t>(f->K) * (f->F + 1);
+  if (kind == TI_OUTPUT_CONTRIB || kind == TI_OUTPUT_CONTRIB_APPROX)
+    return static_cast<int64_t>(f->K) * (f->F + 1);
   if (kind == TI_OUTPUT_INTERACT) return static_cast<int64_t>(f->K) * (f->F + 1) * (f->F + 1);
   if (kind == TI_OUTPUT_PREDICT && f->transform == TI_TRANSFORM_ARGMAX) return 1;
   return f->K;
@@ -472,6 +475,8 @@ int grow(void** buf, size_t* cap, size_t need, bool pinned = false) {
 
 int launch_any(ti_forest* f, int slot, const void* X, int xdt, int64_t rows, int32_t cols,
                int64_t stride, int kind, void* out, hipStream_t stream);
+int launch_approx(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows, int32_t cols,
+                  int64_t stride, void* out, int64_t out_ld, hipStream_t stream);
 
 // Host copies into / out of pinned staging: large copies split over threads
 // (one thread moves ~10 GB/s from pageable memory; PCIe Gen5 x16 takes ~55).
@@ -504,14 +509,16 @@ int64_t chunk_rows(size_t row_bytes) {
   return r;
 }
 
-// The chunk of one call.  Every kind but TI_OUTPUT_INTERACT sizes it by the
-// input row, as above.  An interaction row is K * (F + 1)^2 outputs, far
-// wider than its input (C2: 3,364 B against 112 B), and the lanes hold a
-// chunk of output as well: there TI_CHUNK_MB bounds the wider of the two
-// rows, in whole 64-row waves (the interaction kernels have no 512-row tile).
+// The chunk of one call.  Every kind but TI_OUTPUT_INTERACT and
+// TI_OUTPUT_CONTRIB_APPROX sizes it by the input row, as above.  An
+// interaction row is K * (F + 1)^2 outputs, far wider than its input (C2:
+// 3,364 B against 112 B), and the lanes hold a chunk of output as well: there
+// TI_CHUNK_MB bounds the wider of the two rows, in whole 64-row waves (the
+// interaction kernels have no 512-row tile).  Approximate contributions do the
+// same with their K * (F + 1) outputs (their pass 2 has 64-row tiles too).
 int64_t chunk_rows_for(const ti_forest* f, int xdt, int64_t stride, int kind) {
   const size_t x_row = static_cast<size_t>(stride) * dtype_size(xdt);
-  if (kind != TI_OUTPUT_INTERACT) return chunk_rows(x_row);
+  if (kind != TI_OUTPUT_INTERACT && kind != TI_OUTPUT_CONTRIB_APPROX) return chunk_rows(x_row);
   const size_t o_row = dtype_size(output_dtype(f, kind)) * static_cast<size_t>(output_width(f, kind));
   const int mb = env_int("TI_CHUNK_MB", 64);
   const int64_t r = static_cast<int64_t>((static_cast<size_t>(std::max(mb, 1)) << 20) /
@@ -811,6 +818,21 @@ int launch_chunked(ti_forest* f, int slot, const void* X, int xdt, int64_t rows,
     }
     return TI_OK;
   }
+  if (kind == TI_OUTPUT_CONTRIB_APPROX) {
+    // F + 1 columns a group, written by each part's pass 2 straight into its
+    // groups' columns of the [rows, K * (F + 1)] output, as above: not through
+    // the shared scratch and 2-D copy of TI_OUTPUT_CONTRIB below.  Vector-leaf
+    // parts hold every tree and walk it once each.
+    const int64_t cw = f->F + 1;
+    for (size_t c = 0; c < f->parts.size(); ++c) {
+      ti_forest* p = f->parts[c].get();
+      const int rc = launch_approx(p, *p->devs[slot], X, xdt, rows, cols, stride,
+                                   static_cast<unsigned char*>(out) + f->part_k0[c] * cw * as,
+                                   f->K * cw, stream);
+      if (rc) return rc;
+    }
+    return TI_OK;
+  }
   const int64_t cw = kind == TI_OUTPUT_CONTRIB ? f->F + 1 : 1;   // columns per group
   for (auto& p : f->parts)
     tmp_bytes = std::max(tmp_bytes, static_cast<size_t>(rows) *
@@ -924,8 +946,117 @@ int launch_linear(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t
   return rc;
 }
 
+// Approximate contributions (treeinfer_approx.h): two stream-ordered passes per
+// row block.  Pass 1 is the forest's own walk with TI_OUTPUT_LEAF into a
+// [rows_block, T] int32 scratch, bounded as launch_linear bounds its own (1 GiB;
+// TI_APPROX_SCRATCH_MB is the developer knob, 0: one tile a block); pass 2
+// (approx_contrib_kernel) adds the reached leaves' terms and writes the rows
+// through out_ld, the elements between two output rows.
+constexpr int64_t kApproxWorkgroupTarget = 1536;        // 256 CUs x 6 workgroups (C2's LDS)
+constexpr int kApproxMaxSlices = 32;
+constexpr uint64_t kApproxPartBytesMax = 64ull << 20;   // the slices' partials of one row block
+
+int launch_approx(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows, int32_t cols,
+                  int64_t stride, void* out, int64_t out_ld, hipStream_t stream) {
+  if (f->approx_refused)
+    return fail(TI_ERR_UNSUPPORTED,
+                f->approx_refused == 2
+                    ? "TI_OUTPUT_CONTRIB_APPROX of a forest with linear leaves (a leaf has no one "
+                      "value to take node means of)"
+                    : "approximate contributions need node covers (ti_forest_desc.cover)");
+  if (rows <= 0) return TI_OK;
+  int rc = ensure_approx(f);
+  if (rc) return rc;
+  constexpr int R = ti::kApproxRows;
+  const int64_t W = static_cast<int64_t>(f->K) * (f->F + 1);
+  const int n_tiles = static_cast<int>((W + ti::kApproxCols - 1) / ti::kApproxCols);
+  const int col_tile = static_cast<int>((W + n_tiles - 1) / n_tiles);
+  const size_t lds = static_cast<size_t>(col_tile) * ti::kApproxPitch * 8 +
+                     static_cast<size_t>(R) * ti::kLinPitch * 4;
+  using ApproxFn = void (*)(ti::ApproxArgs);
+  const ApproxFn fn = f->accum == TI_F64 ? ti::approx_contrib_kernel<double, double>
+                                         : ti::approx_contrib_kernel<float, float>;
+  rc = ensure_lds_attr(d.device, reinterpret_cast<KernelFn>(fn));
+  if (rc) return rc;
+  occ_note(reinterpret_cast<KernelFn>(fn), R, lds);
+  const size_t xs = dtype_size(xdt), as = dtype_size(f->accum);
+  const int64_t row_bytes = static_cast<int64_t>(4) * f->T;
+  int64_t rows_block = (static_cast<int64_t>(std::max(env_int("TI_APPROX_SCRATCH_MB", 1024), 0)) << 20) / row_bytes;
+  rows_block = std::max<int64_t>(R, rows_block / R * R);
+  const int64_t rows_max = std::min(rows, rows_block);
+  // Tree slices: a block of few rows is too few single-wave workgroups for 256
+  // CUs with six of them each, so its trees are cut into slices of whole
+  // 32-tree id chunks until about that many workgroups run; the slices' raw
+  // float64 sums [slices][rows][W] (at most 64 MiB, else fewer slices) are
+  // added in slice order by approx_slices_kernel.  TI_APPROX_SLICES (developer
+  // knob) forces the count (1: none).
+  const int64_t n_chunks = (f->T + ti::kLinTC - 1) / ti::kLinTC;
+  const int64_t wgs = (rows_max + R - 1) / R * n_tiles;
+  const int force_slices = env_int("TI_APPROX_SLICES", 0);
+  int64_t want = force_slices > 0 ? force_slices : kApproxWorkgroupTarget / wgs;
+  while (want > 1 && static_cast<uint64_t>(want) * rows_max * W * 8 > kApproxPartBytesMax) --want;
+  want = std::max<int64_t>(1, std::min({want, n_chunks, int64_t(kApproxMaxSlices)}));
+  const int32_t slice_chunks = static_cast<int32_t>((n_chunks + want - 1) / want);
+  const int slices = static_cast<int>((n_chunks + slice_chunks - 1) / slice_chunks);
+  int32_t* ids = nullptr;
+  if (hipMallocAsync(reinterpret_cast<void**>(&ids), static_cast<size_t>(rows_max * row_bytes),
+                     stream) != hipSuccess)
+    return fail(TI_ERR_NOMEM, "leaf-id scratch allocation failed");
+  double* part = nullptr;
+  if (slices > 1 && hipMallocAsync(reinterpret_cast<void**>(&part),
+                                   static_cast<size_t>(slices * rows_max * W) * 8, stream) != hipSuccess) {
+    (void)hipFreeAsync(ids, stream);
+    return fail(TI_ERR_NOMEM, "slice partials allocation failed");
+  }
+  for (int64_t r0 = 0; r0 < rows && rc == TI_OK; r0 += rows_block) {
+    const int64_t nb = std::min(rows_block, rows - r0);
+    const void* xb = static_cast<const unsigned char*>(X) + static_cast<size_t>(r0 * stride) * xs;
+    rc = launch(f, d, xb, xdt, nb, cols, stride, TI_OUTPUT_LEAF, ids, stream);
+    if (rc) break;
+    ti::ApproxArgs a;
+    a.leaf_ids = ids;
+    a.leaves = d.approx_leaves;
+    a.terms = d.approx_terms;
+    a.leaf_base = d.approx_leaf_base;
+    a.bias = d.approx_bias;
+    a.n_rows = nb;
+    a.n_trees = f->T;
+    a.width = static_cast<int32_t>(W);
+    a.f1 = f->F + 1;
+    a.col_tile = col_tile;
+    a.n_col_tiles = n_tiles;
+    a.divisor = f->divisor;
+    a.out = static_cast<unsigned char*>(out) + static_cast<size_t>(r0 * out_ld) * as;
+    a.out_ld = out_ld;
+    a.slice_chunks = slice_chunks;
+    a.part = part;
+    const int64_t grid = (nb + R - 1) / R;
+    if (grid > 0x7fffffff) rc = fail(TI_ERR_INVALID, "too many rows for one launch");
+    if (rc) break;
+    hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(grid), static_cast<unsigned>(std::min(n_tiles, 65535)),
+                                static_cast<unsigned>(slices)),
+                       dim3(R), lds, stream, a);
+    if (slices > 1) {
+      const int64_t n = nb * W;
+      if (f->accum == TI_F64)
+        hipLaunchKernelGGL(ti::approx_slices_kernel<double>, dim3(static_cast<unsigned>((n + 255) / 256)),
+                           dim3(256), 0, stream, a, slices);
+      else
+        hipLaunchKernelGGL(ti::approx_slices_kernel<float>, dim3(static_cast<unsigned>((n + 255) / 256)),
+                           dim3(256), 0, stream, a, slices);
+    }
+    if (hipGetLastError() != hipSuccess) rc = fail(TI_ERR_DEVICE, "approximate contributions launch failed");
+  }
+  (void)hipFreeAsync(ids, stream);
+  if (part) (void)hipFreeAsync(part, stream);
+  return rc;
+}
+
 int launch_any(ti_forest* f, int slot, const void* X, int xdt, int64_t rows, int32_t cols,
                int64_t stride, int kind, void* out, hipStream_t stream) {
+  if (kind == TI_OUTPUT_CONTRIB_APPROX && f->parts.empty())
+    return launch_approx(f, *f->devs[slot], X, xdt, rows, cols, stride, out, output_width(f, kind),
+                         stream);
   if (kind == TI_OUTPUT_CONTRIB && f->linear)
     return fail(TI_ERR_UNSUPPORTED,
                 "TI_OUTPUT_CONTRIB of a forest with linear leaves (LightGBM itself refuses "
@@ -1068,6 +1199,7 @@ int ti_forest_create(const ti_forest_desc* desc, const int32_t* devices, int32_t
   if ((rc = choose_layout(desc, f.get()))) return rc;
   if (desc->lin_offset && (rc = pack_linear(desc, f->host.get()))) return rc;
   keep_shap_source(desc, f.get());
+  keep_approx_source(desc, f.get());
   for (int i = 0; i < n_devices; ++i) {
     f->devs.emplace_back(new DeviceForest());
     rc = upload_device(f.get(), *f->devs.back(), devices[i]);
@@ -1163,7 +1295,7 @@ int ti_forest_set_option(ti_forest* f, int32_t option, int64_t value) {
 int ti_output_shape(const ti_forest* f, int32_t kind, int64_t n_rows, int64_t* out_len,
                     int32_t* out_dtype) {
   if (!f || !out_len || !out_dtype) return fail(TI_ERR_INVALID, "null argument");
-  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_INTERACT) return fail(TI_ERR_INVALID, "bad output kind");
+  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_CONTRIB_APPROX) return fail(TI_ERR_INVALID, "bad output kind");
   if (n_rows < 0) return fail(TI_ERR_INVALID, "negative n_rows");
   *out_len = n_rows * output_width(f, kind);
   *out_dtype = output_dtype(f, kind);
@@ -1174,7 +1306,7 @@ static int check_call(const ti_forest* f, const void* X, int32_t xdt, int64_t ro
                       int64_t stride, int32_t kind, const void* out, int64_t out_len) {
   if (!f) return fail(TI_ERR_INVALID, "null forest");
   if (xdt != TI_F32 && xdt != TI_F64) return fail(TI_ERR_INVALID, "x_dtype must be TI_F32 or TI_F64");
-  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_INTERACT) return fail(TI_ERR_INVALID, "bad output kind");
+  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_CONTRIB_APPROX) return fail(TI_ERR_INVALID, "bad output kind");
   if (rows < 0) return fail(TI_ERR_INVALID, "negative n_rows");
   if (rows == 0) return TI_OK;
   if (!X || !out) return fail(TI_ERR_INVALID, "null data pointer");

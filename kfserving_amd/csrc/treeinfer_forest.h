@@ -33,6 +33,10 @@ using ti::HeapNode;
 using ti::KArgs;
 using ti::KernelFn;
 
+namespace ti {
+struct ApproxLeaf;   // treeinfer_approx.h
+}
+
 // ---------------------------------------------------------- TreeSHAP paths
 // Every root-to-leaf path of every tree, with the splits on one feature
 // merged into one element (the unique path xgboost's TreeShap keeps: a
@@ -270,6 +274,14 @@ struct ShapPtrs {
   int64_t* shap_tab_off = nullptr;   // [paths] first coefficient of each path
 };
 
+// Approximate-contribution tables (treeinfer_approx.h: ensure_approx)
+struct ApproxPtrs {
+  int64_t* approx_leaf_base = nullptr;       // [T + 1] first leaf record of each tree
+  ti::ApproxLeaf* approx_leaves = nullptr;   // per (tree, leaf id) {begin, count}
+  void* approx_terms = nullptr;              // {delta, column}, float or double deltas
+  double* approx_bias = nullptr;             // [K]
+};
+
 // ti_predict scratch: device buffers + pinned host staging (grown x2)
 struct ScratchBufs {
   void* x_buf = nullptr;
@@ -290,15 +302,16 @@ struct ScratchBufs {
   size_t lane_x_cap = 0, lane_o_cap = 0;
 };
 
-// One replica.  Three groups of device memory, each a plain aggregate of
+// One replica.  Four groups of device memory, each a plain aggregate of
 // pointers (bases, so d.heap32 reads as before) reset by one assignment: the
-// forest's arrays and the TreeSHAP tables, freed from the record of what their
-// uploads allocated (forest_mem / shap_mem), and the scratch buffers, which
-// grow() reallocates and free_scratch frees.
-struct DeviceForest : ForestPtrs, ShapPtrs, ScratchBufs {
+// forest's arrays, the TreeSHAP tables and the approximate-contribution
+// tables, freed from the record of what their uploads allocated (forest_mem /
+// shap_mem / approx_mem), and the scratch buffers, which grow() reallocates and
+// free_scratch frees.
+struct DeviceForest : ForestPtrs, ShapPtrs, ApproxPtrs, ScratchBufs {
   int device = -1;
   hipStream_t stream = nullptr;
-  DeviceAllocs forest_mem, shap_mem;
+  DeviceAllocs forest_mem, shap_mem, approx_mem;
   std::atomic<int32_t> shap_tab_state{0};   // 0 not tried, 1 built, -1 failed or over the cap:
                                      // contributions use the extend / unwind kernel
   // TI_OUTPUT_INTERACT scratch (launch_interact: contributions + partials of
@@ -476,5 +489,17 @@ struct ti_forest {
   std::vector<uint32_t> h_shap_cat;          // the category sets of all paths
   std::vector<double> h_path_leaf, h_shap_bias;
   std::atomic<int64_t> lin_scratch_mb{1024};   // TI_OPT_LINEAR_SCRATCH_MB
+  // Approximate contributions (TI_OUTPUT_CONTRIB_APPROX, treeinfer_approx.h):
+  // approx_refused = 1 without covers, 2 with linear leaves.  The tables are
+  // built and uploaded on the first call (ensure_approx, under shap_mu) from
+  // this host copy of the arrays they read, which goes once they are resident.
+  int32_t approx_refused = 0;
+  std::atomic<bool> approx_ready{false};
+  struct ApproxSource {
+    std::vector<int64_t> tree_offset;
+    std::vector<int32_t> tree_group, feature, left, right, leaf_id;
+    std::vector<double> leaf_value, cover, base_margin;
+  };
+  std::unique_ptr<ApproxSource> approx_src;
   std::vector<std::unique_ptr<DeviceForest>> devs;
 };

@@ -18,10 +18,10 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .forest import (Forest, OUT_CONTRIB, OUT_INTERACT, OUT_LEAF, OUT_MARGIN, OUT_PREDICT, TI_F32, TI_F64,
-                     TI_I32)
+from .forest import (Forest, OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_INTERACT, OUT_LEAF, OUT_MARGIN,
+                     OUT_PREDICT, TI_F32, TI_F64, TI_I32)
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 _LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("TREEINFER_LIB", os.path.join(_LIB_DIR, "libtreeinfer.so"))
 
@@ -326,4 +326,5 @@ class DeviceForest:
 __all__ = ["DeviceForest", "TreeInferError", "prepare_input", "load_library", "device_count", "default_devices",
            "OPT_SHAP_TABLE_ROWS", "OPT_SHAP_TABLE_MB", "OPT_HOST_REGISTER", "OPT_LINEAR_SCRATCH_MB",
            "EXPORTED_SYMBOLS", "OUT_MARGIN", "OUT_PREDICT", "OUT_LEAF", "OUT_CONTRIB", "OUT_INTERACT",
+           "OUT_CONTRIB_APPROX",
            "TI_F32", "TI_F64", "TI_I32"]

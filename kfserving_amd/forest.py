@@ -46,6 +46,7 @@ OUT_PREDICT = 1
 OUT_LEAF = 2
 OUT_CONTRIB = 3     # TreeSHAP contributions [rows, K * (F + 1)], bias last per group
 OUT_INTERACT = 4    # SHAP interaction values [rows, K * (F + 1) * (F + 1)] (pred_interactions)
+OUT_CONTRIB_APPROX = 5   # approximate (Saabas) contributions, laid out as OUT_CONTRIB (approx_contribs)
 
 # LightGBM missing types (decision_type bits 2-3)
 MISSING_NONE = 0
@@ -264,7 +265,7 @@ class Forest:
     def output_width(self, kind: int) -> int:
         if kind == OUT_LEAF:
             return self.n_trees
-        if kind == OUT_CONTRIB:
+        if kind in (OUT_CONTRIB, OUT_CONTRIB_APPROX):
             return self.n_groups * (self.n_features + 1)
         if kind == OUT_INTERACT:
             return self.n_groups * (self.n_features + 1) ** 2

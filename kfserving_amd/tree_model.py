@@ -15,7 +15,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from .engine import DeviceForest, prepare_input
-from .forest import OUT_CONTRIB, OUT_INTERACT, OUT_PREDICT, Forest
+from .forest import OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_INTERACT, OUT_PREDICT, Forest
 
 
 class GPUForestMixin:
@@ -100,8 +100,18 @@ class GPUForestMixin:
         A request with top-level ``"pred_interactions": true`` (xgboost's
         name) gets SHAP interaction values instead (TI_OUTPUT_INTERACT):
         [rows, F + 1, F + 1], or [rows, K, F + 1, F + 1] for K groups; every
-        row of a matrix sums to the contribution the plain request returns."""
+        row of a matrix sums to the contribution the plain request returns.
+
+        A request with top-level ``"approx_contribs": true`` (xgboost's name)
+        gets the approximate (Saabas) contributions (TI_OUTPUT_CONTRIB_APPROX),
+        shaped as the plain request's; they are served where TreeSHAP is not
+        (XGBoost categorical splits, any width and depth).  Both keys together
+        (approximate interactions) are an error."""
         try:
+            approx = isinstance(request, dict) and request.get("approx_contribs") is True
+            if approx and request.get("pred_interactions") is True:
+                raise ValueError('"approx_contribs" and "pred_interactions" together '
+                                 "(approximate interaction values) are not served")
             X = self.request_matrix(request)
             f = self._forest
             if isinstance(request, dict) and request.get("pred_interactions") is True:
@@ -110,7 +120,7 @@ class GPUForestMixin:
                 m = m.reshape((m.shape[0], f.n_groups, n, n) if f.n_groups > 1
                               else (m.shape[0], n, n))
                 return {"explanations": m.tolist()}
-            c = self.predict_matrix(X, OUT_CONTRIB)
+            c = self.predict_matrix(X, OUT_CONTRIB_APPROX if approx else OUT_CONTRIB)
             if f.n_groups > 1:
                 c = c.reshape(c.shape[0], f.n_groups, f.n_features + 1)
             return {"explanations": c.tolist()}

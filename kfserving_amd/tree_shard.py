@@ -18,7 +18,8 @@ sums, so margins differ from the one-device order by rounding only
 ``gather``, so each rank sends its block once and only the root receives), not
 summed, and stay exact.  TreeSHAP contributions are additive over trees too (each shard's bias
 holds its trees' expected values; the base margin lives on the root's shard)
-and are reduced the same way.
+and are reduced the same way, and so are the approximate (Saabas) ones
+(``OUT_CONTRIB_APPROX``).
 
 The reference has no counterpart (its predict is single-process per model,
 python/xgbserver/xgbserver/model.py:43-50); the API follows DeviceForest's.
@@ -29,7 +30,8 @@ from typing import Callable, List, Optional, Tuple
 
 import numpy as np
 
-from .forest import OUT_CONTRIB, OUT_INTERACT, OUT_LEAF, OUT_MARGIN, OUT_PREDICT, TI_F32, Forest
+from .forest import (OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_INTERACT, OUT_LEAF, OUT_MARGIN, OUT_PREDICT,
+                     TI_F32, Forest)
 
 
 def partition_trees(forest: Forest, world: int) -> List[Tuple[int, int]]:
@@ -92,7 +94,7 @@ class TreeShardedForest:
         """X: [rows, cols] tensor on this rank's device (every rank passes the
         same rows).  Returns the full output on the root (PREDICT and LEAF
         shaped as DeviceForest.predict returns them, MARGIN [rows, K], CONTRIB
-        [rows, K * (F + 1)]) and None elsewhere."""
+        and CONTRIB_APPROX [rows, K * (F + 1)]) and None elsewhere."""
         if kind == OUT_INTERACT:   # it would fall through to the margin path below
             raise ValueError("kind OUT_INTERACT (SHAP interaction values) is not served "
                              "tree-sharded; use DeviceForest.predict")
@@ -106,7 +108,7 @@ class TreeShardedForest:
         dev = X.device
         if kind == OUT_LEAF:
             return self._gather_leaves(X, rows, cols, xdt, stream)
-        part_kind = OUT_CONTRIB if kind == OUT_CONTRIB else OUT_MARGIN
+        part_kind = kind if kind in (OUT_CONTRIB, OUT_CONTRIB_APPROX) else OUT_MARGIN
         width = f.output_width(part_kind)
         part = torch.empty((rows, width), dtype=self._dtype(kind), device=dev)
         self.engine.predict_device(X.data_ptr(), xdt, rows, cols, cols, part_kind,
