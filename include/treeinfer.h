@@ -333,7 +333,13 @@ int ti_predict(ti_forest* forest, const void* X, int32_t x_dtype, int64_t n_rows
 /* Device-resident predict on one of the forest's devices (device_slot indexes
  * the devices passed to ti_forest_create).  X and out are device pointers on
  * that device; the kernels are enqueued on `hip_stream` (a hipStream_t, NULL =
- * the default stream) and the call returns without synchronising. */
+ * the default stream) and the call returns without synchronising, with one
+ * exception: a call that needs more scratch than the replica holds (the first
+ * call of a kind, a larger batch; forests of more than 16 groups, TreeSHAP,
+ * approximate contributions, linear leaves) allocates it with hipFree /
+ * hipMalloc, which may synchronise the device.  The scratch stays with the
+ * replica until ti_forest_destroy and is not part of
+ * ti_forest_info.device_bytes. */
 int ti_predict_device(ti_forest* forest, int32_t device_slot, const void* X,
                       int32_t x_dtype, int64_t n_rows, int32_t n_cols,
                       int64_t row_stride, int32_t output_kind, void* out,

@@ -53,6 +53,11 @@ void free_device(DeviceForest& d) {
   d.interact_done = nullptr;
   d.interact_buf = nullptr;
   d.interact_cap = 0;
+  for (auto& b : d.scratch.bufs) {
+    if (b.done) (void)hipEventDestroy(b.done);
+    if (b.p) (void)hipFree(b.p);
+  }
+  d.scratch.bufs.clear();
   if (d.stream) (void)hipStreamDestroy(d.stream);
   d.stream = nullptr;
   d.device = -1;
@@ -790,17 +795,14 @@ __global__ void scatter_cols_kernel(const int32_t* __restrict__ src, int64_t row
 }
 
 // Device path of a chunked forest: each part writes its margin columns (or
-// leaf-id columns) through a stream-ordered scratch buffer, then the output
-// transform runs over the assembled [rows, K] margins.
+// leaf-id columns) through a scratch buffer of the replica's (CallScratch),
+// then the output transform runs over the assembled [rows, K] margins.
 int launch_chunked(ti_forest* f, int slot, const void* X, int xdt, int64_t rows, int32_t cols,
                    int64_t stride, int kind, void* out, hipStream_t stream) {
   const size_t as = f->accum == TI_F64 ? 8 : 4;
   const int threads = 256;
   if (kind == TI_OUTPUT_LEAF && f->LW != 1)   // vector leaves: every part holds every tree
     return launch_any(f->parts[0].get(), slot, X, xdt, rows, cols, stride, kind, out, stream);
-  void* tmp = nullptr;
-  void* marg = nullptr;
-  int32_t* dmap = nullptr;
   int rc = TI_OK;
   size_t tmp_bytes = 0;
   if (kind == TI_OUTPUT_INTERACT) {
@@ -837,14 +839,15 @@ int launch_chunked(ti_forest* f, int slot, const void* X, int xdt, int64_t rows,
   for (auto& p : f->parts)
     tmp_bytes = std::max(tmp_bytes, static_cast<size_t>(rows) *
                                         (kind == TI_OUTPUT_LEAF ? 4 * p->T : as * p->K * cw));
-  TI_HIP(hipMallocAsync(&tmp, tmp_bytes, stream));
+  // the replica that serves the slot: the first part's (base_forest)
+  DeviceForest& sd = *f->parts[0]->devs[slot];
+  ScratchHold tmp_buf(sd, stream), marg_buf(sd, stream);   // given back behind the last kernel below
+  if (!tmp_buf.take(tmp_bytes)) return fail(TI_ERR_NOMEM, "part scratch allocation failed");
+  void* tmp = tmp_buf.p;
   const bool transform = kind == TI_OUTPUT_PREDICT && f->transform != TI_TRANSFORM_IDENTITY;
-  if (transform) {
-    if (hipMallocAsync(&marg, static_cast<size_t>(rows) * f->K * as, stream) != hipSuccess) {
-      (void)hipFreeAsync(tmp, stream);
-      return fail(TI_ERR_NOMEM, "margin scratch allocation failed");
-    }
-  }
+  if (transform && !marg_buf.take(static_cast<size_t>(rows) * f->K * as))
+    return fail(TI_ERR_NOMEM, "margin scratch allocation failed");
+  void* marg = marg_buf.p;
   void* mdst = transform ? marg : out;
   for (size_t c = 0; c < f->parts.size() && rc == TI_OK; ++c) {
     ti_forest* p = f->parts[c].get();
@@ -852,9 +855,10 @@ int launch_chunked(ti_forest* f, int slot, const void* X, int xdt, int64_t rows,
       rc = launch_any(p, slot, X, xdt, rows, cols, stride, kind, tmp, stream);
       if (rc) break;
       const std::vector<int32_t>& map = f->part_trees[c];
-      if (hipMallocAsync(reinterpret_cast<void**>(&dmap), map.size() * 4, stream) != hipSuccess ||
-          hipMemcpyAsync(dmap, map.data(), map.size() * 4, hipMemcpyHostToDevice, stream) !=
-              hipSuccess) {
+      ScratchHold map_buf(sd, stream);   // given back behind scatter_cols_kernel
+      int32_t* dmap = map_buf.take(map.size() * 4) ? static_cast<int32_t*>(map_buf.p) : nullptr;
+      if (!dmap || hipMemcpyAsync(dmap, map.data(), map.size() * 4, hipMemcpyHostToDevice, stream) !=
+                       hipSuccess) {
         rc = fail(TI_ERR_DEVICE, "leaf map upload failed");
         break;
       }
@@ -862,8 +866,6 @@ int launch_chunked(ti_forest* f, int slot, const void* X, int xdt, int64_t rows,
       hipLaunchKernelGGL(scatter_cols_kernel, dim3(static_cast<unsigned>((n + threads - 1) / threads)),
                          dim3(threads), 0, stream, static_cast<const int32_t*>(tmp), rows, p->T,
                          dmap, f->T, static_cast<int32_t*>(out));
-      (void)hipFreeAsync(dmap, stream);
-      dmap = nullptr;
     } else {
       const int pk = kind == TI_OUTPUT_CONTRIB ? TI_OUTPUT_CONTRIB : TI_OUTPUT_MARGIN;
       rc = launch_any(p, slot, X, xdt, rows, cols, stride, pk, tmp, stream);
@@ -886,8 +888,6 @@ int launch_chunked(ti_forest* f, int slot, const void* X, int xdt, int64_t rows,
                          static_cast<float*>(out));
     if (hipGetLastError() != hipSuccess) rc = fail(TI_ERR_DEVICE, "transform launch failed");
   }
-  (void)hipFreeAsync(tmp, stream);
-  if (marg) (void)hipFreeAsync(marg, stream);
   return rc;
 }
 
@@ -917,10 +917,10 @@ int launch_linear(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t
   int64_t rows_block = (f->lin_scratch_mb.load() << 20) / row_bytes;
   rows_block = std::max<int64_t>(block, rows_block / block * block);
   rows_block = std::min(rows_block, (rows + block - 1) / block * block);
-  int32_t* ids = nullptr;
-  if (hipMallocAsync(reinterpret_cast<void**>(&ids),
-                     static_cast<size_t>(std::min(rows, rows_block) * row_bytes), stream) != hipSuccess)
+  ScratchHold ids_buf(d, stream);   // given back behind the last pass 2
+  if (!ids_buf.take(static_cast<size_t>(std::min(rows, rows_block) * row_bytes)))
     return fail(TI_ERR_NOMEM, "leaf-id scratch allocation failed");
+  int32_t* ids = static_cast<int32_t*>(ids_buf.p);
   const size_t out_row = static_cast<size_t>(output_width(f, kind)) * 8;
   for (int64_t r0 = 0; r0 < rows && rc == TI_OK; r0 += rows_block) {
     const int64_t nb = std::min(rows_block, rows - r0);
@@ -942,7 +942,6 @@ int launch_linear(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t
                        stream, a, la);
     if (hipGetLastError() != hipSuccess) rc = fail(TI_ERR_DEVICE, "linear leaf launch failed");
   }
-  (void)hipFreeAsync(ids, stream);
   return rc;
 }
 
@@ -998,16 +997,13 @@ int launch_approx(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t
   want = std::max<int64_t>(1, std::min({want, n_chunks, int64_t(kApproxMaxSlices)}));
   const int32_t slice_chunks = static_cast<int32_t>((n_chunks + want - 1) / want);
   const int slices = static_cast<int>((n_chunks + slice_chunks - 1) / slice_chunks);
-  int32_t* ids = nullptr;
-  if (hipMallocAsync(reinterpret_cast<void**>(&ids), static_cast<size_t>(rows_max * row_bytes),
-                     stream) != hipSuccess)
+  ScratchHold ids_buf(d, stream), part_buf(d, stream);   // given back behind the last pass 2
+  if (!ids_buf.take(static_cast<size_t>(rows_max * row_bytes)))
     return fail(TI_ERR_NOMEM, "leaf-id scratch allocation failed");
-  double* part = nullptr;
-  if (slices > 1 && hipMallocAsync(reinterpret_cast<void**>(&part),
-                                   static_cast<size_t>(slices * rows_max * W) * 8, stream) != hipSuccess) {
-    (void)hipFreeAsync(ids, stream);
+  int32_t* ids = static_cast<int32_t*>(ids_buf.p);
+  if (slices > 1 && !part_buf.take(static_cast<size_t>(slices * rows_max * W) * 8))
     return fail(TI_ERR_NOMEM, "slice partials allocation failed");
-  }
+  double* part = static_cast<double*>(part_buf.p);
   for (int64_t r0 = 0; r0 < rows && rc == TI_OK; r0 += rows_block) {
     const int64_t nb = std::min(rows_block, rows - r0);
     const void* xb = static_cast<const unsigned char*>(X) + static_cast<size_t>(r0 * stride) * xs;
@@ -1047,8 +1043,6 @@ int launch_approx(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t
     }
     if (hipGetLastError() != hipSuccess) rc = fail(TI_ERR_DEVICE, "approximate contributions launch failed");
   }
-  (void)hipFreeAsync(ids, stream);
-  if (part) (void)hipFreeAsync(part, stream);
   return rc;
 }
 

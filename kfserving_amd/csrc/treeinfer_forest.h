@@ -302,6 +302,32 @@ struct ScratchBufs {
   size_t lane_x_cap = 0, lane_o_cap = 0;
 };
 
+// The scratch of calls in flight on one replica (launch_chunked's part columns,
+// TreeSHAP's slice partials and accumulator, the leaf ids of the linear and
+// approximate passes): hipMalloc buffers of the replica's own, taken for a
+// call and given back behind its last kernel with an event.  A call takes a
+// buffer whose event has completed, or one given back on the call's own
+// stream, and makes its stream wait for that event either way (a wait that
+// orders nothing new, unless a new stream got a destroyed one's handle);
+// otherwise it gets another buffer, so calls on different streams (the host
+// pipeline's lanes, a caller's streams) never wait for each other.  Buffers
+// grow to the size asked for, rounded up to 64 KiB, never shrink, and are
+// freed with the replica; growing one frees and allocates device memory,
+// which may synchronise the device.  Not the runtime's stream-ordered pool
+// (hipMallocAsync): on the HIP 7.2 runtime its blocks came back to later calls
+// of other sizes while still holding live data ("Call scratch").
+struct CallScratch {
+  struct Buf {
+    void* p = nullptr;
+    size_t cap = 0;
+    hipEvent_t done = nullptr;     // recorded when the buffer was given back
+    hipStream_t last = nullptr;    // on this stream
+    bool held = false;
+  };
+  std::mutex mu;
+  std::vector<Buf> bufs;
+};
+
 // One replica.  Four groups of device memory, each a plain aggregate of
 // pointers (bases, so d.heap32 reads as before) reset by one assignment: the
 // forest's arrays, the TreeSHAP tables and the approximate-contribution
@@ -321,8 +347,86 @@ struct DeviceForest : ForestPtrs, ShapPtrs, ApproxPtrs, ScratchBufs {
   void* interact_buf = nullptr;
   size_t interact_cap = 0;
   hipEvent_t interact_done = nullptr;
+  CallScratch scratch;
   int64_t bytes = 0;
   std::mutex mu;
+};
+
+// A buffer of at least `bytes` for work enqueued on `stream` (device current),
+// or nullptr when the device has no memory for it.
+inline void* scratch_take(DeviceForest& d, size_t bytes, hipStream_t stream) {
+  std::lock_guard<std::mutex> lk(d.scratch.mu);
+  bytes = (std::max<size_t>(bytes, 1) + 65535) & ~size_t(65535);
+  CallScratch::Buf* pick = nullptr;
+  for (auto& b : d.scratch.bufs) {
+    if (b.held) continue;
+    const bool done = hipEventQuery(b.done) == hipSuccess;   // never recorded: done
+    if (!done) (void)hipGetLastError();
+    // one that fits, the smallest such; else one to regrow, which must be
+    // idle on the device (the largest such)
+    if (b.cap >= bytes ? !(done || b.last == stream) : !done) continue;
+    if (!pick || (b.cap >= bytes ? (pick->cap < bytes || b.cap < pick->cap)
+                                 : (pick->cap < bytes && b.cap > pick->cap)))
+      pick = &b;
+  }
+  if (!pick) {
+    CallScratch::Buf b;
+    if (hipEventCreateWithFlags(&b.done, hipEventDisableTiming) != hipSuccess) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+    d.scratch.bufs.push_back(b);
+    pick = &d.scratch.bufs.back();
+  }
+  if (pick->cap < bytes) {
+    // its event has completed, so nothing reads or writes it; hipFree and
+    // hipMalloc may still synchronise the device (ti_predict_device's note)
+    if (pick->p) (void)hipFree(pick->p);
+    pick->p = nullptr;
+    pick->cap = 0;
+    if (hipMalloc(&pick->p, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      pick->p = nullptr;
+      return nullptr;
+    }
+    pick->cap = bytes;
+  } else {
+    (void)hipStreamWaitEvent(stream, pick->done, 0);
+  }
+  pick->held = true;
+  pick->last = stream;
+  return pick->p;
+}
+
+inline void scratch_give(DeviceForest& d, void* p, hipStream_t stream) {
+  if (!p) return;
+  std::lock_guard<std::mutex> lk(d.scratch.mu);
+  for (auto& b : d.scratch.bufs)
+    if (b.p == p) {
+      (void)hipEventRecord(b.done, stream);
+      b.last = stream;
+      b.held = false;
+    }
+}
+
+// One scratch buffer for the scope of a call: given back, behind whatever the
+// call enqueued on the stream, when the scope ends on any path.
+struct ScratchHold {
+  DeviceForest& d;
+  hipStream_t s;
+  void* p = nullptr;
+  ScratchHold(DeviceForest& d_, hipStream_t s_) : d(d_), s(s_) {}
+  ScratchHold(const ScratchHold&) = delete;
+  ScratchHold& operator=(const ScratchHold&) = delete;
+  bool take(size_t bytes) {
+    p = scratch_take(d, bytes, s);
+    return p != nullptr;
+  }
+  void give() {
+    scratch_give(d, p, s);
+    p = nullptr;
+  }
+  ~ScratchHold() { give(); }
 };
 
 // Binned heap layout (3): one image per input dtype (the ranks differ: float32

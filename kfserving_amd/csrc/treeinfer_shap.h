@@ -971,10 +971,10 @@ int launch_contrib(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_
     // unwind arithmetic (2.2e5 vs 2.9e5): profiles/r3_shap_table.jsonl
     const bool want_tab = use_table && f->shap_tab_mt != 0 && rows <= f->shap_tab_rows;
     if (want_tab && d.shap_tab_state == 0) ensure_shap_table(f, d);
-    double* part = nullptr;
-    if (slices > 1)
-      TI_HIP(hipMallocAsync(reinterpret_cast<void**>(&part),
-                            static_cast<size_t>(slices * W * rows) * 8, stream));
+    ScratchHold part_buf(d, stream);   // given back behind contrib_slices_kernel
+    if (slices > 1 && !part_buf.take(static_cast<size_t>(slices * W * rows) * 8))
+      return fail(TI_ERR_NOMEM, "slice partials allocation failed");
+    double* part = static_cast<double*>(part_buf.p);
 #define TI_CONTRIB_REG(XT_, ACC_, MT_, N_)                                                          \
   do {                                                                                         \
     const bool tab_ = want_tab && d.shap_tab_state == 1 &&                                     \
@@ -1029,14 +1029,16 @@ int launch_contrib(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_
 #undef TI_CONTRIB_REG_N
 #undef TI_CONTRIB_REG
     TI_HIP(hipGetLastError());
-    if (part) TI_HIP(hipFreeAsync(part, stream));
     return TI_OK;
   }
   double* acc = nullptr;
+  ScratchHold acc_buf(d, stream);   // given back behind contrib_kernel
   if (f->accum == TI_F64) {
     acc = static_cast<double*>(out);
   } else {
-    TI_HIP(hipMallocAsync(reinterpret_cast<void**>(&acc), static_cast<size_t>(rows * W) * 8, stream));
+    if (!acc_buf.take(static_cast<size_t>(rows * W) * 8))
+      return fail(TI_ERR_NOMEM, "contributions accumulator allocation failed");
+    acc = static_cast<double*>(acc_buf.p);
   }
   TI_HIP(hipMemsetAsync(acc, 0, static_cast<size_t>(rows * W) * 8, stream));
   const size_t lds = static_cast<size_t>(2 * f->shap_maxl + 1) * 64 * 8;
@@ -1078,7 +1080,6 @@ int launch_contrib(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_
                          d.shap_cat_refs, d.shap_cat_words);
   }
   TI_HIP(hipGetLastError());
-  if (acc != out) TI_HIP(hipFreeAsync(acc, stream));
   return TI_OK;
 }
 

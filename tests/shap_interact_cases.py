@@ -125,17 +125,22 @@ def want(name):
     return w
 
 
-def predict(dev, X, kind=OUT_INTERACT):
+def predict(dev, X, kind=OUT_INTERACT, stride=None):
     """ti_predict on X in its own dtype (DeviceForest.predict would convert it
-    to the forest's input type), [rows, width]."""
+    to the forest's input type), [rows, width].  `stride` > cols passes the
+    rows at that pitch, NaN between them."""
     X = np.ascontiguousarray(X)
     assert X.dtype in (np.float32, np.float64)
     rows, cols = X.shape
+    if stride is not None:
+        wide = np.full((rows, stride), np.nan, dtype=X.dtype)
+        wide[:, :cols] = X
+        X = wide
     width = dev.forest.output_width(kind)
     out = np.empty(rows * width, dtype=dev.forest.output_dtype(kind))
     xdt = TI_F32 if X.dtype == np.float32 else TI_F64
     engine._check(dev._lib, dev._lib.ti_predict(dev._handle, ctypes.c_void_p(X.ctypes.data), xdt,
-                                                rows, cols, cols, kind,
+                                                rows, cols, stride or cols, kind,
                                                 ctypes.c_void_p(out.ctypes.data), out.size))
     return out.reshape(rows, width)
 
