@@ -63,7 +63,8 @@ constexpr uint32_t kShapCatOutside = 16u;   // a value no bit of the set covers 
 struct ShapElem {
   int32_t feature;
   uint32_t flags;
-  double lo;        // follows iff lo < x <= hi (non-NaN, non-zero x)
+  double lo;        // follows iff !(x <= lo) && x <= hi (non-NaN, non-zero x); NaN: no lower
+                    //   bound, so that -inf follows a path that only turns left on the feature
   double hi;
   double zf;        // zero fraction
 };

@@ -16,7 +16,7 @@
 __device__ __forceinline__ bool shap_follow_num(const ShapElem& e, double x) {
   if (x != x) return (e.flags & kShapNanOk) != 0;
   if (x == 0.0) return (e.flags & kShapZeroOk) != 0;
-  return !(e.flags & kShapEmpty) && e.lo < x && x <= e.hi;
+  return !(e.flags & kShapEmpty) && !(x <= e.lo) && x <= e.hi;   // lo NaN: unbounded below
 }
 
 // LightGBM's rule (ti::cat_left) against the element's set: codes are trunc(x)
@@ -692,7 +692,7 @@ struct ShapBuilder {
       const bool left = side == 0;
       const int32_t child = left ? d->left[g] : d->right[g];
       const std::vector<Elem> saved = cur;
-      Elem el{ShapElem{fe, kShapNanOk | kShapZeroOk, -INFINITY, INFINITY, 1.0}, {}};
+      Elem el{ShapElem{fe, kShapNanOk | kShapZeroOk, std::nan(""), INFINITY, 1.0}, {}};
       for (size_t i = 0; i < cur.size(); ++i)
         if (cur[i].e.feature == fe) {   // unwind the earlier split on fe (interval and set),
           el = cur[i];                  // re-extend at the end
@@ -709,7 +709,7 @@ struct ShapBuilder {
           if (std::isnan(t)) e.flags |= kShapEmpty;
           else e.hi = std::min(e.hi, t);
         } else if (!std::isnan(t)) {
-          e.lo = std::max(e.lo, t);
+          e.lo = std::isnan(e.lo) ? t : std::max(e.lo, t);   // -inf itself is a bound: x > -inf
         }
         if (nan_left != left) e.flags &= ~kShapNanOk;
         if (zero_left != left) e.flags &= ~kShapZeroOk;

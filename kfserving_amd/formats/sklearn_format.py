@@ -4,7 +4,9 @@ Replaces the estimator the reference unpickles at
 python/sklearnserver/sklearnserver/model.py:38 (``joblib.load``) and calls at
 :50 (``self._model.predict``).  Supported: DecisionTree{Regressor,Classifier},
 RandomForest{Regressor,Classifier}, ExtraTrees{Regressor,Classifier} with one
-output, and GradientBoosting{Regressor,Classifier} (forest_from_gradient_boosting).
+output, GradientBoosting{Regressor,Classifier} (forest_from_gradient_boosting)
+and HistGradientBoosting{Regressor,Classifier}
+(forest_from_hist_gradient_boosting).
 
 Predict semantics encoded (installed sklearn 1.7.2,
 sklearn/tree/_tree.pyx:979-997 and sklearn/ensemble/_forest.py:723-736,
@@ -13,6 +15,12 @@ sklearn/tree/_tree.pyx:979-997 and sklearn/ensemble/_forest.py:723-736,
 regressors sum ``value[leaf]`` in float64 in estimator order and divide by
 n_estimators; classifiers do the same with the per-leaf class-fraction
 vector and take the first argmax.
+
+HistGradientBoosting is the one family that keeps X in float64 and carries
+categorical splits (ensemble/_hist_gradient_boosting/gradient_boosting.py,
+_predictor.pyx, common.pyx): its forests declare ``input_dtype`` TI_F64 and
+restate sklearn's categorical node as the XGBoost-rule node the kernels
+already evaluate -- see forest_from_hist_gradient_boosting.
 """
 from __future__ import annotations
 
@@ -20,8 +28,8 @@ from typing import Tuple
 
 import numpy as np
 
-from ..forest import (Forest, NODE_NAN_LEFT, TI_F32, TI_F64, T_ARGMAX, T_IDENTITY, T_STEP,
-                      concat_trees)
+from ..forest import (Forest, NODE_NAN_LEFT, TI_F32, TI_F64, T_ARGMAX, T_EXP, T_HINGE, T_IDENTITY,
+                      T_STEP, concat_trees)
 
 TREE_LEAF = -1
 
@@ -151,8 +159,198 @@ def forest_from_gradient_boosting(est) -> Forest:
     ).contiguous()
 
 
+_HGB_NAMES = ("HistGradientBoostingRegressor", "HistGradientBoostingClassifier")
+_HGB_NODE_FIELDS = ("value", "count", "feature_idx", "num_threshold", "missing_go_to_left",
+                    "left", "right", "is_leaf", "is_categorical", "bitset_idx")
+_HGB_MAX_CATEGORY = 1 << 24     # the XGBoost rule reads [0, 2^24) as categories
+
+
+def _hgb_categories(est, is_cat: np.ndarray) -> dict:
+    """Raw column -> the sorted raw categories the estimator's ordinal encoder
+    learned (a trailing NaN dropped): a value's code is its index here.  They
+    become bit positions of the canonical bitsets, so they must be integers in
+    [0, 2^24) -- the range the XGBoost rule reads as categories at all."""
+    enc = est._preprocessor.named_transformers_["encoder"]
+    cols = np.flatnonzero(is_cat)
+    if len(enc.categories_) != cols.size:
+        raise TypeError("HistGradientBoosting encoder and is_categorical_ disagree "
+                        "(a pickle of another sklearn version?)")
+    out = {}
+    for col, c in zip(cols, enc.categories_):
+        c = np.asarray(c)
+        if c.dtype.kind not in "fiub":
+            raise ValueError(f"categorical feature {int(col)}: categories of dtype {c.dtype} are "
+                             "not numeric (string categories are not supported)")
+        c = c.astype(np.float64)
+        c = c[~np.isnan(c)]
+        if c.size and c.min() < 0:
+            raise ValueError(f"categorical feature {int(col)}: negative category {c.min():g} "
+                             "(categories must be integers in [0, 2^24))")
+        if not np.all(c == np.floor(c)):
+            bad = c[c != np.floor(c)][0]
+            raise ValueError(f"categorical feature {int(col)}: non-integer category {bad:g} "
+                             "(categories must be integers in [0, 2^24))")
+        if c.size and c.max() >= _HGB_MAX_CATEGORY:
+            raise ValueError(f"categorical feature {int(col)}: category {c.max():g} >= 2^24 "
+                             "(categories must be integers in [0, 2^24))")
+        out[int(col)] = c.astype(np.int64)
+    return out
+
+
+
+def _bitset_members(words: np.ndarray, n: int) -> np.ndarray:
+    """Bits 0..n-1 of a uint32 bitset as booleans."""
+    j = np.arange(n)
+    return ((np.asarray(words, dtype=np.uint32)[j // 32] >> (j % 32).astype(np.uint32)) & 1) != 0
+
+
+def forest_from_hist_gradient_boosting(est) -> Forest:
+    """HistGradientBoosting{Regressor,Classifier} (installed sklearn 1.7.2,
+    ensemble/_hist_gradient_boosting/gradient_boosting.py ``_raw_predict`` /
+    ``_predict_iterations``, _predictor.pyx ``_predict_one_from_raw_data``):
+
+        raw[:, k] = _baseline_prediction[0, k]
+        for each iteration, for k: raw[:, k] += value[leaf]          (float64)
+
+    with X kept in float64 (NaN and, on numerical columns, infinity allowed).
+    A numerical node sends NaN to ``missing_go_to_left``'s side and otherwise
+    goes left iff ``x <= num_threshold`` -- the canonical compare, +inf
+    thresholds included.  The leaf payload is ``value`` (the learning rate is
+    already in it), an iteration's K trees are output groups 0..K-1 in
+    iteration order, so the sums are bit-identical.  predict: regressor the
+    inverse link (identity, or exp for poisson / gamma); binary classifier
+    ``raw > 0`` (T_HINGE, not GradientBoosting's ``>= 0``); multiclass first
+    argmax.
+
+    Categorical features: the estimator ordinal-encodes them (``_preprocessor``)
+    and moves them to the front, so ``feature_idx`` is mapped back to the raw
+    column and the code-space bitsets to raw-value space (bit C[j] for code j
+    of the feature's sorted categories C).  sklearn's node goes left iff the
+    code is in the node's left set, else right iff the category is known, else
+    (NaN, unknown) to ``missing_go_to_left``'s side.  Both cases are the
+    XGBoost rule (NaN by flag; x < 0 or x >= 2^24 left; in set right):
+
+    * ``missing_go_to_left`` = 1: set = known & ~left, NAN_LEFT; left-set,
+      unknown and invalid values all go left, where missing goes.
+    * ``missing_go_to_left`` = 0: children swapped, set = left, NAN_LEFT; in
+      set is the new right (old left), everything else the new left (old right).
+
+    Categories must therefore be integers in [0, 2^24): a node's bitset is as
+    long as its largest chosen category needs (at most 2 MiB), and no layout
+    asks for a lower cap (a forest whose sets do not fit the categorical heap
+    runs on the explicit kernel).  Anything else is refused here.
+
+    One gap: a non-integer value on a categorical column (3.5) is an unknown
+    category to sklearn, while the canonical rule truncates it (category 3).
+    The serving layer replaces such values by NaN before the walk
+    (SKLearnModel.request_matrix); callers of the engine itself must do the
+    same.  TreeSHAP contributions (OUT_CONTRIB) of a model with categorical
+    splits stay refused like every XGBoost-rule forest; OUT_CONTRIB_APPROX
+    serves them."""
+    from .xgboost_format import _concat_categories, _set_categorical
+    try:
+        predictors = est._predictors
+        baseline = np.asarray(est._baseline_prediction, dtype=np.float64)
+        pre = est._preprocessor
+        is_cat = est.is_categorical_
+        F = int(est.n_features_in_)
+        K = int(est.n_trees_per_iteration_)
+        classifier = hasattr(est, "classes_")
+        link = None if classifier else type(est._loss.link).__name__
+        known_sets = f_idx_map = None
+        if pre is not None:
+            known_sets, f_idx_map = est._bin_mapper.make_known_categories_bitsets()
+        for it in predictors:
+            for p in it:
+                missing = [n for n in _HGB_NODE_FIELDS if n not in p.nodes.dtype.names]
+                if missing:
+                    raise AttributeError(f"predictor nodes lack {missing}")
+                getattr(p, "raw_left_cat_bitsets")
+    except AttributeError as e:
+        raise TypeError(f"{type(est).__name__} lacks the private attributes of sklearn 1.7 "
+                        f"this loader reads (a pickle of another sklearn version?): {e}") from e
+    if baseline.shape != (1, K) or any(len(it) != K for it in predictors):
+        raise TypeError(f"{type(est).__name__}: unexpected baseline / predictor shapes "
+                        "(a pickle of another sklearn version?)")
+    if pre is None:
+        perm = np.arange(F)
+        cats = {}
+    else:
+        is_cat = np.asarray(is_cat, dtype=bool)
+        perm = np.concatenate([np.flatnonzero(is_cat), np.flatnonzero(~is_cat)])
+        cats = _hgb_categories(est, is_cat)
+    if classifier:
+        transform = T_HINGE if K == 1 else T_ARGMAX
+    elif link == "IdentityLink":
+        transform = T_IDENTITY
+    elif link == "LogLink":
+        transform = T_EXP
+    else:
+        raise TypeError(f"{type(est).__name__} with link {link} is not supported")
+
+    canon, groups = [], []
+    for it in predictors:
+        for k, p in enumerate(it):
+            nd = p.nodes
+            n = nd.shape[0]
+            leaf = nd["is_leaf"] != 0
+            mgl = nd["missing_go_to_left"] != 0
+            iscat = ~leaf & (nd["is_categorical"] != 0)
+            if iscat.any() and pre is None:
+                raise TypeError("categorical nodes in an estimator without a preprocessor")
+            fidx = np.where(leaf, 0, nd["feature_idx"]).astype(np.int64)
+            if fidx.size and (fidx.min() < 0 or fidx.max() >= F):
+                raise ValueError("split feature index outside the estimator's features")
+            left = np.where(leaf, -1, nd["left"].astype(np.int64))
+            right = np.where(leaf, -1, nd["right"].astype(np.int64))
+            swap = iscat & ~mgl
+            t = {
+                "feature": np.where(leaf, -1, perm[fidx]),
+                "threshold": np.where(leaf | iscat, 0.0, nd["num_threshold"]),
+                "flags": np.where(~leaf & (mgl | iscat), NODE_NAN_LEFT, 0).astype(np.uint8),
+                "left": np.where(swap, right, left),
+                "right": np.where(swap, left, right),
+                "leaf_id": np.arange(n),
+                "leaf_value": np.where(leaf, nd["value"], 0.0)[:, None],
+                "cover": nd["count"].astype(np.float64),
+            }
+            sets = {}
+            for i in np.flatnonzero(iscat):
+                C = cats[int(perm[fidx[i]])]
+                chosen = _bitset_members(p.raw_left_cat_bitsets[int(nd["bitset_idx"][i])], C.size)
+                if mgl[i]:
+                    known = _bitset_members(known_sets[int(f_idx_map[fidx[i]])], C.size)
+                    chosen = known & ~chosen
+                sets[int(i)] = C[chosen]
+            if sets:
+                _set_categorical(t, sets)
+            canon.append(t)
+            groups.append(k)
+    cat = concat_trees(canon, 1)
+    cat_bits, cat_offset, cat_nwords = _concat_categories(canon)
+    return Forest(
+        n_features=F, n_groups=K, leaf_width=1, accum_dtype=TI_F64,
+        base_first=True, lgb_zero_map=False,
+        tree_offset=cat["tree_offset"], tree_group=np.asarray(groups, dtype=np.int32),
+        feature=cat["feature"], threshold=cat["threshold"], flags=cat["flags"],
+        left=cat["left"], right=cat["right"], leaf_id=cat["leaf_id"],
+        leaf_value=cat["leaf_value"], base_margin=baseline[0].copy(), average_divisor=1.0,
+        cover=cat["cover"], transform=transform, transform_param=1.0,
+        input_dtype=TI_F64, library="sklearn", objective=type(est).__name__,
+        cat_bits=cat_bits, cat_offset=cat_offset, cat_nwords=cat_nwords,
+        meta={"classes": np.asarray(est.classes_) if classifier else None,
+              "hist_gradient_boosting": True,
+              # who validates the width: the ColumnTransformer when there is one
+              "validator": type(est).__name__ if pre is None else type(pre).__name__,
+              "categorical_features": np.flatnonzero(is_cat) if pre is not None
+              else np.zeros(0, dtype=np.int64)},
+    ).contiguous()
+
+
 def forest_from_sklearn(est) -> Forest:
     """Flatten a fitted sklearn tree ensemble."""
+    if type(est).__name__ in _HGB_NAMES:
+        return forest_from_hist_gradient_boosting(est)
     if type(est).__name__ in ("GradientBoostingRegressor", "GradientBoostingClassifier"):
         return forest_from_gradient_boosting(est)
     members, average = _estimators(est)

@@ -4,8 +4,9 @@ Same constructor (name, model_dir) and ``instances`` request format.  ``load``
 finds model.joblib / .pkl / .pickle like the reference (:21-41; these files
 are the user's own model, loaded with joblib exactly as the reference does)
 or the pickle-free ``model.npz`` tree-array export, and flattens a
-RandomForest / ExtraTrees / DecisionTree estimator; ``predict`` runs the
-trees through libtreeinfer where the reference called ``_model.predict``.
+RandomForest / ExtraTrees / DecisionTree / GradientBoosting /
+HistGradientBoosting estimator; ``predict`` runs the trees through
+libtreeinfer where the reference called ``_model.predict``.
 """
 import os
 from typing import Dict
@@ -58,6 +59,8 @@ class SKLearnModel(GPUForestMixin, KFModel):  # pylint:disable=c-extension-no-me
         """sklearn's validate_data checks on the ``instances`` array."""
         f = self._forest
         X = np.asarray(self._array(request), dtype=np.float64)
+        if f.meta.get("hist_gradient_boosting"):
+            return self._hgb_matrix(X)
         if X.ndim != 2:
             raise ValueError("Expected 2D array, got %dD array instead" % X.ndim)
         if X.shape[1] != f.n_features:
@@ -74,6 +77,41 @@ class SKLearnModel(GPUForestMixin, KFModel):  # pylint:disable=c-extension-no-me
                              "dtype('float32').")
         return X
 
+    def _hgb_matrix(self, X: np.ndarray) -> np.ndarray:
+        """HistGradientBoosting's ``_preprocess_X(reset=False)``: X stays
+        float64, NaN and (on numerical columns) infinity pass, nothing is cast
+        to float32.  Without categorical features validate_data checks the
+        shape; with them the estimator's ColumnTransformer does (its name is
+        in the messages) and its ordinal encoder rejects infinity on a
+        categorical column.  A value the encoder does not know is missing: the
+        forest's bitsets say so for integers (forest_from_hist_gradient_boosting),
+        and non-integer values become NaN here, in a copy."""
+        f = self._forest
+        who, F = f.meta["validator"], f.n_features
+        cat = np.asarray(f.meta["categorical_features"], dtype=np.int64)
+        if cat.size and X.ndim == 1:
+            raise ValueError("X does not contain any features, but %s is expecting %d features"
+                             % (who, F))
+        if cat.size == 0 and X.ndim < 2:
+            raise ValueError("Expected 2D array, got %s array instead"
+                             % ("1D" if X.ndim else "scalar"))
+        if X.ndim > 2 and (cat.size == 0 or X.shape[1] == F):
+            raise ValueError("Found array with dim %d, while dim <= 2 is required by %s."
+                             % (X.ndim, f.objective))
+        if X.ndim < 2 or X.shape[1] != F:
+            raise ValueError("X has %d features, but %s is expecting %d features as input."
+                             % (X.shape[1] if X.ndim > 1 else 0, who, F))
+        if cat.size:
+            C = X[:, cat]
+            if np.isinf(C).any():
+                raise ValueError("Input contains infinity or a value too large for "
+                                 "dtype('float64').")
+            stray = C != np.floor(C)         # NaN too, which stays NaN
+            if stray.any():
+                X = X.copy()
+                X[:, cat] = np.where(stray, np.nan, C)
+        return X
+
     def predict_tensor(self, X: np.ndarray) -> np.ndarray:
         """A V2 tensor through the same checks and label mapping as predict."""
         f = self._forest
@@ -87,9 +125,14 @@ class SKLearnModel(GPUForestMixin, KFModel):  # pylint:disable=c-extension-no-me
     def native_v1_transform(self):
         """The native HTTP route's element rule and checks (kfhttp.h): the
         float32 cast; a value that overflows it, or a NaN the estimator
-        rejects, sends the request to predict's own checks."""
+        rejects, sends the request to predict's own checks.
+        HistGradientBoosting forests declare none, so the application answers
+        them: the categorical columns' infinity check and non-integer rule
+        (_hgb_matrix) are no element rule of the native route, and its plain
+        float64 rule has not been held against _hgb_matrix on an
+        ``instances`` route even for models without categorical features."""
         f = self._forest
-        if f is None:
+        if f is None or f.meta.get("hist_gradient_boosting"):
             return None
         return (1 << 8) | (0 if f.meta.get("allow_nan", True) else (1 << 9))
 
