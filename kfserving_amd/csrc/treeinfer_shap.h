@@ -146,6 +146,16 @@ constexpr int64_t kShapWaveTarget = 65536;        // 64-row waves per contrib la
 constexpr int64_t kShapMinPathsPerSlice = 256;
 constexpr int64_t kShapMaxSlices = 64;
 constexpr uint64_t kShapPartBytesMax = 2ull << 30;
+// The longest path, in MAXN, whose extend / unwind arithmetic a float32
+// forest does in float32.  The unwound sums cancel, and the loss grows with
+// the path: against the float64 reference, chains of 16 distinct features
+// measured 3.7e-7 (contributions) and 9.4e-7 (interactions) of the row's
+// scale, of 17 1.8e-6 and 1.9e-6, of 32 1.5e-2 and 4.3e-2, where float64
+// arithmetic gives the float32 output's own rounding, 6e-8
+// (profiles/shap_edge_error_before.jsonl; xgboost's own bst_float TreeShap loses
+// 9e-3 on the same 32-element chains).  So the MAXN = 32 instantiations are
+// float64 only.
+constexpr int kShapF32MaxN = 16;
 // TAB: the per-element coefficients UnwoundPathSum x (one - zero) of every
 // path and every pattern of one fractions were computed once per forest
 // (shap_table_kernel, the same expressions in the same MT arithmetic), so a
@@ -950,7 +960,7 @@ int launch_contrib(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_
     // registers + LDS accumulators: no scratch accumulator, no memset
     const int maxn = f->shap_maxl <= 8 ? 8 : f->shap_maxl <= 16 ? 16 : 32;
     const int force_f64 = env_int("TI_SHAP_F64", 0);
-    const bool f32_math = f->accum != TI_F64 && !force_f64;
+    const bool f32_math = f->accum != TI_F64 && !force_f64 && maxn <= kShapF32MaxN;
     const size_t lds_w = static_cast<size_t>(W) * 64 * (f32_math ? 4 : 8);
     const unsigned grid_r = static_cast<unsigned>((rows + 63) / 64);
     if (rows == 0) return TI_OK;
@@ -1012,20 +1022,27 @@ int launch_contrib(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_
     else if (maxn == 16) TI_CONTRIB_REG(XT_, ACC_, MT_, 16); \
     else TI_CONTRIB_REG(XT_, ACC_, MT_, 32);                 \
   } while (0)
+#define TI_CONTRIB_REG_F32(XT_)                              \
+  do {                                                       \
+    if (maxn == 8) TI_CONTRIB_REG(XT_, float, float, 8);     \
+    else TI_CONTRIB_REG(XT_, float, float, 16);              \
+  } while (0)
     // Path arithmetic in the forest's accumulator type: float64 for LightGBM
     // and sklearn; float32 for XGBoost, whose TreeShap keeps its path
-    // elements and contributions in bst_float (TI_SHAP_F64=1 forces
-    // float64).  Each slice accumulates in that type in LDS (float32 halves
-    // the LDS per workgroup: 2x workgroups per CU); slices sum in float64.
+    // elements and contributions in bst_float, on paths of at most
+    // kShapF32MaxN elements (longer ones, and TI_SHAP_F64=1, take float64).
+    // Each slice accumulates in that type in LDS (float32 halves the LDS per
+    // workgroup: 2x workgroups per CU); slices sum in float64.
     if (xdt == TI_F32) {
       if (f->accum == TI_F64) TI_CONTRIB_REG_N(float, double, double);
-      else if (f32_math) TI_CONTRIB_REG_N(float, float, float);
+      else if (f32_math) TI_CONTRIB_REG_F32(float);
       else TI_CONTRIB_REG_N(float, float, double);
     } else {
       if (f->accum == TI_F64) TI_CONTRIB_REG_N(double, double, double);
-      else if (f32_math) TI_CONTRIB_REG_N(double, float, float);
+      else if (f32_math) TI_CONTRIB_REG_F32(double);
       else TI_CONTRIB_REG_N(double, float, double);
     }
+#undef TI_CONTRIB_REG_F32
 #undef TI_CONTRIB_REG_N
 #undef TI_CONTRIB_REG
     TI_HIP(hipGetLastError());
@@ -1118,7 +1135,7 @@ int launch_interact(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64
   const size_t xs = xdt == TI_F64 ? 8 : 4;
   const int64_t n_paths = static_cast<int64_t>(d.shap_paths ? 1 : 0) * f->shap_npaths;
   const int maxn = f->shap_maxl <= 8 ? 8 : f->shap_maxl <= 16 ? 16 : 32;
-  const bool f32_math = f->accum != TI_F64 && !env_int("TI_SHAP_F64", 0);
+  const bool f32_math = f->accum != TI_F64 && !env_int("TI_SHAP_F64", 0) && maxn <= kShapF32MaxN;
   const int cpb = kShapLdsW / F1;                    // conditioned features a block
   const int nb = F > 0 ? (F + cpb - 1) / cpb : 0;    // blocks a group
   const size_t lds = static_cast<size_t>(std::min(cpb, std::max(F, 1)) * F1) * 64 * (f32_math ? 4 : 8);
@@ -1203,17 +1220,23 @@ int launch_interact(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64
     else if (maxn == 16) TI_INTERACT(XT_, MT_, 16);   \
     else TI_INTERACT(XT_, MT_, 32);                   \
   } while (0)
+#define TI_INTERACT_F32(XT_)                          \
+  do {                                                \
+    if (maxn == 8) TI_INTERACT(XT_, float, 8);        \
+    else TI_INTERACT(XT_, float, 16);                 \
+  } while (0)
   for (int64_t r0 = 0; r0 < rows && rc == TI_OK; r0 += rb) {
     const int64_t n = std::min(rb, rows - r0);
     const unsigned grid_r = static_cast<unsigned>((n + 63) / 64);
     const void* xb = static_cast<const unsigned char*>(X) + static_cast<size_t>(r0 * stride) * xs;
     if (nb > 0) {
-      // path arithmetic in the forest's accumulator type, as for contributions
+      // path arithmetic in the forest's accumulator type, float64 on paths of
+      // more than kShapF32MaxN elements, as for contributions
       if (xdt == TI_F32) {
-        if (f32_math) TI_INTERACT_N(float, float);
+        if (f32_math) TI_INTERACT_F32(float);
         else TI_INTERACT_N(float, double);
       } else {
-        if (f32_math) TI_INTERACT_N(double, float);
+        if (f32_math) TI_INTERACT_F32(double);
         else TI_INTERACT_N(double, double);
       }
       if (rc) break;
@@ -1230,6 +1253,7 @@ int launch_interact(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64
                          (int32_t)slices, n, K, F, reinterpret_cast<const float*>(pb), d.shap_bias,
                          f->divisor, reinterpret_cast<float*>(ob), out_ld);
   }
+#undef TI_INTERACT_F32
 #undef TI_INTERACT_N
 #undef TI_INTERACT
   if (rc == TI_OK && hipGetLastError() != hipSuccess)
