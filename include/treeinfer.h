@@ -82,6 +82,28 @@
  *   output groups, and leaf_id = 0 .. L-1 within each tree (LightGBM's).
  *   TI_OUTPUT_CONTRIB of a linear forest is TI_ERR_UNSUPPORTED (fatal upstream),
  *   and so is TI_OUTPUT_INTERACT.
+ *
+ * Pre-steps (ABI 9; the scaler and imputer steps of a sklearn Pipeline in front
+ * of its forest): when desc.n_pre_steps = S > 0, every input element is
+ * transformed before any split reads it.  Take element v of type XT (float32
+ * or float64, the call's x_dtype) in column f.  For s = 0 .. S-1, in order,
+ * with c = pre_const[s * F + f]:
+ *     TI_PRE_FILL_NAN:  if v is NaN then v = (XT)c
+ *     TI_PRE_SUB:       v = (XT)((double)v - c)
+ *     TI_PRE_DIV:       v = (XT)((double)v / c)
+ *     TI_PRE_MUL:       v = (XT)((double)v * c)
+ *     TI_PRE_ADD:       v = (XT)((double)v + c)
+ *   Each arithmetic step is one IEEE float64 operation, rounded to nearest
+ *   even and never fused with a neighbour; for float32 input its result is then
+ *   rounded to float32 (what numpy's in-place `X -= mean_` does to a float32
+ *   array).  Finally x' = (float)v, rounded to nearest even, overflow giving
+ *   +-inf, and the forest walks x' as float32 input by the rules above.
+ *   This holds for every output kind: contributions and interactions are those
+ *   of the forest on the transformed columns (the steps are per column, so
+ *   column f still means feature f).  A forest with pre-steps needs
+ *   n_cols == n_features at predict (TI_ERR_INVALID otherwise); S > 16, and
+ *   pre-steps together with linear leaves, are TI_ERR_UNSUPPORTED; an unknown
+ *   op code, or S > 0 with a null pre_op or pre_const, is TI_ERR_INVALID.
  */
 #ifndef TREEINFER_H_
 #define TREEINFER_H_
@@ -92,7 +114,7 @@
 extern "C" {
 #endif
 
-#define TI_ABI_VERSION 8
+#define TI_ABI_VERSION 9
 
 /* return codes */
 #define TI_OK               0
@@ -123,6 +145,14 @@ extern "C" {
 #define TI_TRANSFORM_SIGNSQUARE  6  /* sign(x) * x * x (LightGBM sqrt)       */
 #define TI_TRANSFORM_LOG1PEXP    7  /* log(1 + exp(x)) (LightGBM xentlambda) */
 #define TI_TRANSFORM_STEP        8  /* x >= 0 ? 1 : 0 (sklearn binary GradientBoosting label) */
+
+/* pre-step operations (ABI 9; ti_forest_desc.pre_op), see the rule above */
+#define TI_PRE_FILL_NAN 0  /* NaN -> the column's constant                  */
+#define TI_PRE_SUB      1  /* v - c                                         */
+#define TI_PRE_DIV      2  /* v / c (IEEE division)                         */
+#define TI_PRE_MUL      3  /* v * c                                         */
+#define TI_PRE_ADD      4  /* v + c                                         */
+#define TI_PRE_MAX_STEPS 16
 
 /* what ti_predict writes */
 #define TI_OUTPUT_MARGIN   0  /* raw score (after base/average), [rows, K]     */
@@ -232,6 +262,13 @@ typedef struct ti_forest_desc {
   const int32_t* lin_feature; /* [M]   raw column of each term                      */
   const double*  lin_coeff;   /* [M]   coefficient of each term                     */
   const double*  lin_const;   /* [N]   constant of node n's linear model            */
+  /* pre-steps (ABI 9); 0 / NULL when the forest has none.  Replaces the
+   * transformers in front of the final estimator of a sklearn Pipeline
+   * (Pipeline[:-1].transform). */
+  int32_t n_pre_steps;        /* S; 0: none                                         */
+  int32_t reserved1;
+  const int32_t* pre_op;      /* [S]     TI_PRE_* of each step                      */
+  const double*  pre_const;   /* [S * F] constant of step s for column f            */
 } ti_forest_desc;
 
 typedef struct ti_forest ti_forest;   /* opaque, owns device memory */
@@ -270,6 +307,7 @@ typedef struct ti_forest_info {
   int32_t linear;             /* ABI 6: 1 the forest has linear leaves, 0 not        */
   int64_t shap_table_bytes;   /* device bytes of the built table                     */
   double  shap_table_build_ms;/* host wall time of the last table build             */
+  int32_t pre_steps;          /* ABI 9: pre-steps S applied where X enters (0: none) */
 } ti_forest_info;
 
 /* ti_forest_set_option options (ABI 4) */
@@ -336,8 +374,9 @@ int ti_predict(ti_forest* forest, const void* X, int32_t x_dtype, int64_t n_rows
  * the default stream) and the call returns without synchronising, with one
  * exception: a call that needs more scratch than the replica holds (the first
  * call of a kind, a larger batch; forests of more than 16 groups, TreeSHAP,
- * approximate contributions, linear leaves) allocates it with hipFree /
- * hipMalloc, which may synchronise the device.  The scratch stays with the
+ * approximate contributions, linear leaves, and pre-steps, whose transformed
+ * float32 rows live there) allocates it with hipFree / hipMalloc, which may
+ * synchronise the device.  The scratch stays with the
  * replica until ti_forest_destroy and is not part of
  * ti_forest_info.device_bytes. */
 int ti_predict_device(ti_forest* forest, int32_t device_slot, const void* X,
@@ -356,6 +395,17 @@ int ti_predict_device(ti_forest* forest, int32_t device_slot, const void* X,
  * LGBM_BoosterPredictForMat apply after summing the trees. */
 int ti_transform_device(ti_forest* forest, int32_t device_slot, const void* margin,
                         int64_t n_rows, void* out, int64_t out_len, void* hip_stream);
+
+/* The forest's pre-steps alone (ABI 9), the input-side twin of
+ * ti_transform_device: X as ti_predict_device takes it, out a dense float32
+ * [n_rows, n_cols] device array holding x' of the rule above (for a forest
+ * without pre-steps: the plain conversion to float32).  n_cols must be the
+ * forest's n_features.  Enqueued on hip_stream; returns without synchronising.
+ * Replaces Pipeline[:-1].transform; in the tree-sharded mode each rank may
+ * transform its own rows with it. */
+int ti_pretransform_device(ti_forest* forest, int32_t device_slot, const void* X,
+                           int32_t x_dtype, int64_t n_rows, int32_t n_cols,
+                           int64_t row_stride, float* out, void* hip_stream);
 
 /* Thread-local message for the last failing call on this thread
  * (XGBGetLastError / LGBM_GetLastError). */

@@ -184,7 +184,10 @@ class NativeBatcher:
     @classmethod
     def for_device_forest(cls, dev, max_batch_size: int, max_latency_ms: float,
                           kind: int = OUT_PREDICT, max_inflight: int = 2) -> "NativeBatcher":
-        """A batcher whose model call is libtreeinfer's ti_predict on `dev`."""
+        """A batcher whose model call is libtreeinfer's ti_predict on `dev`.
+        A batch has one element type, the forest's ``input_dtype``: for a
+        sklearn Pipeline forest (TI_F64) float32 rows are widened as they are
+        copied and their pre-steps then run in float64."""
         f = dev.forest
         lib = dev._lib
         return cls(ctypes.cast(lib.ti_predict, ctypes.c_void_p).value, f.n_features,

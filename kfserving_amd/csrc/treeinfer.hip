@@ -21,6 +21,7 @@
 #include "treeinfer_pack.h"
 #include "treeinfer_shap.h"
 #include "treeinfer_approx.h"
+#include "treeinfer_pre.h"
 
 namespace {
 
@@ -124,6 +125,8 @@ int upload_device(const ti_forest* f, DeviceForest& d, int device) {
     up(&d.lin_terms, h.lin_terms);
     up(&d.lin_leaf_base, h.lin_leaf_base);
   }
+  up(&d.pre_op, h.pre_op);
+  up(&d.pre_const, h.pre_const);
   return rc;
 }
 
@@ -1046,8 +1049,9 @@ int launch_approx(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t
   return rc;
 }
 
-int launch_any(ti_forest* f, int slot, const void* X, int xdt, int64_t rows, int32_t cols,
-               int64_t stride, int kind, void* out, hipStream_t stream) {
+// The forest's walk of X as it stands: every kind, every forest shape.
+int launch_walk(ti_forest* f, int slot, const void* X, int xdt, int64_t rows, int32_t cols,
+                int64_t stride, int kind, void* out, hipStream_t stream) {
   if (kind == TI_OUTPUT_CONTRIB_APPROX && f->parts.empty())
     return launch_approx(f, *f->devs[slot], X, xdt, rows, cols, stride, out, output_width(f, kind),
                          stream);
@@ -1069,6 +1073,59 @@ int launch_any(ti_forest* f, int slot, const void* X, int xdt, int64_t rows, int
   if (f->linear && (kind == TI_OUTPUT_MARGIN || kind == TI_OUTPUT_PREDICT))
     return launch_linear(f, *f->devs[slot], X, xdt, rows, cols, stride, kind, out, stream);
   return launch(f, *f->devs[slot], X, xdt, rows, cols, stride, kind, out, stream);
+}
+
+ti_forest* base_forest(ti_forest* f);
+
+// pre_steps_kernel over a batch: S steps with the arrays of replica d (S = 0:
+// the plain conversion to float32), dense float32 [rows, cols] into `out`.
+int launch_pre_steps(const DeviceForest& d, int S, const void* X, int xdt, int64_t rows,
+                     int32_t cols, int64_t stride, float* out, hipStream_t stream) {
+  if (rows <= 0) return TI_OK;
+  ti::PreArgs a;
+  a.X = X;
+  a.out = out;
+  a.ops = d.pre_op;
+  a.consts = d.pre_const;
+  a.row_stride = stride;
+  a.total = static_cast<uint64_t>(rows) * static_cast<uint64_t>(cols);
+  a.n_cols = static_cast<uint32_t>(cols);
+  a.n_steps = S;
+  const uint64_t per_wg = static_cast<uint64_t>(ti::kPreBlock) * ti::kPreUnroll;
+  const uint32_t grid = static_cast<uint32_t>(
+      std::min<uint64_t>((a.total + per_wg - 1) / per_wg, ti::kPreMaxGrid));
+  a.step = grid * ti::kPreBlock;
+  a.step_rows = a.step / a.n_cols;
+  a.step_cols = a.step % a.n_cols;
+  const size_t const_bytes = static_cast<size_t>(S) * cols * 8;
+  const bool lds = const_bytes <= ti::kPreLdsBudget;
+  const size_t lds_bytes = lds ? align16(const_bytes + static_cast<size_t>(S) * 4) : 0;
+  hipLaunchKernelGGL(ti::select_pre(xdt == TI_F64, lds), dim3(grid), dim3(ti::kPreBlock), lds_bytes,
+                     stream, a);
+  TI_HIP(hipGetLastError());
+  return TI_OK;
+}
+
+// Where X enters.  A forest with pre-steps transforms the batch once into a
+// float32 scratch of the slot's replica (given back behind the walk's last
+// kernel) and walks that; its group parts (launch_chunked) and every
+// two-pass kind then read the transformed rows.  A forest without pre-steps
+// goes straight to its walk.
+int launch_any(ti_forest* f, int slot, const void* X, int xdt, int64_t rows, int32_t cols,
+               int64_t stride, int kind, void* out, hipStream_t stream) {
+  if (f->pre_steps <= 0 || rows <= 0)
+    return launch_walk(f, slot, X, xdt, rows, cols, stride, kind, out, stream);
+  if (cols != f->F)
+    return fail(TI_ERR_INVALID, "a forest with pre-steps needs n_cols == n_features (" +
+                                    std::to_string(f->F) + "), got " + std::to_string(cols));
+  DeviceForest& d = *base_forest(f)->devs[slot];
+  ScratchHold xt(d, stream);
+  if (!xt.take(static_cast<size_t>(rows) * cols * 4))
+    return fail(TI_ERR_NOMEM, "pre-step scratch allocation failed");
+  const int rc = launch_pre_steps(d, f->pre_steps, X, xdt, rows, cols, stride,
+                                  static_cast<float*>(xt.p), stream);
+  if (rc) return rc;
+  return launch_walk(f, slot, xt.p, TI_F32, rows, cols, cols, kind, out, stream);
 }
 
 // Split a forest of K > kMaxGroups outputs into parts of at most kMaxGroups
@@ -1135,12 +1192,18 @@ int create_chunked(const ti_forest_desc* d, const std::vector<int>& depth, const
     sd.cat_offset = d->cat_offset ? cat_off.data() : nullptr;
     sd.cat_nwords = d->cat_offset ? cat_nw.data() : nullptr;
     sd.cover = d->cover ? cov.data() : nullptr;
+    if (k0 > 0) {   // the first part's replicas hold the pre-step arrays
+      sd.n_pre_steps = 0;
+      sd.pre_op = nullptr;
+      sd.pre_const = nullptr;
+    }
     ti_forest* part = nullptr;
     const int rc = ti_forest_create(&sd, devices, n_devices, &part);
     if (rc) {
       for (auto& q : f->parts) ti_forest_destroy(q.release());
       return rc;
     }
+    part->pre_steps = 0;   // the parent transforms X once (launch_any); no part does
     f->parts.emplace_back(part);
     f->part_k0.push_back(k0);
     f->part_trees.push_back(std::move(trees));
@@ -1151,7 +1214,7 @@ int create_chunked(const ti_forest_desc* d, const std::vector<int>& depth, const
 }
 
 // The forest whose DeviceForest (stream, staging buffers, lock) serves a slot.
-ti_forest* base_forest(ti_forest* f) {
+ti_forest* base_forest(ti_forest* f) {   // declared above launch_any
   while (!f->parts.empty()) f = f->parts[0].get();
   return f;
 }
@@ -1194,6 +1257,11 @@ int ti_forest_create(const ti_forest_desc* desc, const int32_t* devices, int32_t
   if (desc->lin_offset && (rc = pack_linear(desc, f->host.get()))) return rc;
   keep_shap_source(desc, f.get());
   keep_approx_source(desc, f.get());
+  if (desc->n_pre_steps > 0) {
+    f->host->pre_op.assign(desc->pre_op, desc->pre_op + desc->n_pre_steps);
+    f->host->pre_const.assign(desc->pre_const,
+                              desc->pre_const + static_cast<size_t>(desc->n_pre_steps) * desc->n_features);
+  }
   for (int i = 0; i < n_devices; ++i) {
     f->devs.emplace_back(new DeviceForest());
     rc = upload_device(f.get(), *f->devs.back(), devices[i]);
@@ -1254,6 +1322,7 @@ int ti_forest_get_info(const ti_forest* f, ti_forest_info* info) {
   info->linear = f->linear;
   info->shap_table_bytes = info->shap_table == 1 ? sf->shap_tab_len * sf->shap_tab_mt : 0;
   info->shap_table_build_ms = sf->shap_tab_build_ms;
+  info->pre_steps = f->pre_steps;
   return TI_OK;
 }
 
@@ -1306,6 +1375,9 @@ static int check_call(const ti_forest* f, const void* X, int32_t xdt, int64_t ro
   if (!X || !out) return fail(TI_ERR_INVALID, "null data pointer");
   if (cols <= 0) return fail(TI_ERR_INVALID, "n_cols must be > 0");
   if (stride < cols) return fail(TI_ERR_INVALID, "row_stride < n_cols");
+  if (f->pre_steps > 0 && cols != f->F)
+    return fail(TI_ERR_INVALID, "a forest with pre-steps needs n_cols == n_features (" +
+                                    std::to_string(f->F) + "), got " + std::to_string(cols));
   if (out_len < rows * output_width(f, kind))
     return fail(TI_ERR_INVALID, "output buffer too small: need " +
                                     std::to_string(rows * output_width(f, kind)) + " elements");
@@ -1384,6 +1456,25 @@ int ti_transform_device(ti_forest* f, int32_t slot, const void* margin, int64_t 
                        static_cast<float*>(out));
   TI_HIP(hipGetLastError());
   return TI_OK;
+}
+
+int ti_pretransform_device(ti_forest* f, int32_t slot, const void* X, int32_t xdt, int64_t rows,
+                           int32_t cols, int64_t stride, float* out, void* stream) {
+  if (!f) return fail(TI_ERR_INVALID, "null forest");
+  if (xdt != TI_F32 && xdt != TI_F64) return fail(TI_ERR_INVALID, "x_dtype must be TI_F32 or TI_F64");
+  if (rows < 0) return fail(TI_ERR_INVALID, "negative n_rows");
+  if (rows == 0) return TI_OK;
+  if (!X || !out) return fail(TI_ERR_INVALID, "null data pointer");
+  if (cols != f->F)
+    return fail(TI_ERR_INVALID, "n_cols must be the forest's n_features (" + std::to_string(f->F) + ")");
+  if (stride < cols) return fail(TI_ERR_INVALID, "row_stride < n_cols");
+  ti_forest* bf = base_forest(f);
+  if (slot < 0 || slot >= static_cast<int>(bf->devs.size()))
+    return fail(TI_ERR_INVALID, "device_slot out of range");
+  DeviceForest& d = *bf->devs[slot];
+  TI_HIP(hipSetDevice(d.device));
+  return launch_pre_steps(d, f->pre_steps, X, xdt, rows, cols, stride, out,
+                          static_cast<hipStream_t>(stream));
 }
 
 int ti_predict_device(ti_forest* f, int32_t slot, const void* X, int32_t xdt, int64_t rows,

@@ -261,6 +261,9 @@ struct ForestPtrs {
   ti::LinLeaf* lin_leaves = nullptr;
   ti::LinTerm* lin_terms = nullptr;
   int64_t* lin_leaf_base = nullptr;
+  // pre-steps (treeinfer_pre.h): op codes [S] and constants [S * F]
+  int32_t* pre_op = nullptr;
+  double* pre_const = nullptr;
 };
 
 // TreeSHAP path tables (ensure_shap) and coefficient table (ensure_shap_table)
@@ -507,6 +510,9 @@ struct HostImage {
   std::vector<ti::LinLeaf> lin_leaves;
   std::vector<ti::LinTerm> lin_terms;
   std::vector<int64_t> lin_leaf_base;
+  // pre-steps (ABI 9): the descriptor's op codes [S] and constants [S * F]
+  std::vector<int32_t> pre_op;
+  std::vector<double> pre_const;
 };
 
 }  // namespace
@@ -532,6 +538,10 @@ struct ti_forest {
   int32_t has_cat_xgb = 0;   // ... with XGBoost's rule (TI_NODE_CAT_XGB)
   int32_t has_cat_lgb = 0;   // ... with LightGBM's rule
   int32_t linear = 0;        // linear leaves (ABI 6; pack_linear)
+  // pre-steps (ABI 9) this forest applies where X enters (launch_any).  A
+  // forest split into group parts applies them itself, once, with the arrays
+  // its first part's replicas hold; the parts apply none.
+  int32_t pre_steps = 0;
   // ---- the layout's plan (choose_layout)
   int32_t layout = kLayoutHeap;
   int64_t stride32 = 0, stride64 = 0;

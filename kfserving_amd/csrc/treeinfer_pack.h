@@ -55,6 +55,19 @@ int validate(const ti_forest_desc* d, std::vector<int>* depth_out) {
                   "linear leaves with more than 16 output groups: such forests are split into "
                   "group parts, and the linear tables are not subset per part");
   }
+  if (d->n_pre_steps < 0) return fail(TI_ERR_INVALID, "n_pre_steps must be >= 0");
+  if (d->n_pre_steps > 0) {   // pre-steps (ABI 9)
+    if (!d->pre_op || !d->pre_const) return fail(TI_ERR_INVALID, "pre-steps without pre_op / pre_const");
+    if (d->n_pre_steps > TI_PRE_MAX_STEPS)
+      return fail(TI_ERR_UNSUPPORTED, "more than " + std::to_string(TI_PRE_MAX_STEPS) + " pre-steps");
+    for (int s = 0; s < d->n_pre_steps; ++s)
+      if (d->pre_op[s] < TI_PRE_FILL_NAN || d->pre_op[s] > TI_PRE_ADD)
+        return fail(TI_ERR_INVALID, "unknown pre-step op code " + std::to_string(d->pre_op[s]));
+    if (d->lin_offset)
+      return fail(TI_ERR_UNSUPPORTED,
+                  "pre-steps with linear leaves (the linear models would read the raw columns; no "
+                  "loader produces the combination)");
+  }
   depth_out->assign(d->n_trees, 0);
   std::vector<int> stack_node, stack_depth;
   for (int t = 0; t < d->n_trees; ++t) {
@@ -131,6 +144,7 @@ void fill_model(const ti_forest_desc* desc, const std::vector<int>& depth, ti_fo
       else if (desc->flags[i] & TI_NODE_ZERO_FLIP) f->zero_rule = 1;
     }
   f->linear = desc->lin_offset ? 1 : 0;
+  f->pre_steps = desc->n_pre_steps;
   f->depth = *std::max_element(depth.begin(), depth.end());
 }
 

@@ -21,14 +21,14 @@ import numpy as np
 from .forest import (Forest, OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_INTERACT, OUT_LEAF, OUT_MARGIN,
                      OUT_PREDICT, TI_F32, TI_F64, TI_I32)
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 _LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("TREEINFER_LIB", os.path.join(_LIB_DIR, "libtreeinfer.so"))
 
 EXPORTED_SYMBOLS = (
     "ti_forest_create", "ti_forest_destroy", "ti_forest_get_info", "ti_output_shape",
     "ti_predict", "ti_predict_device", "ti_transform_device", "ti_last_error", "ti_device_count",
-    "ti_abi_version", "ti_forest_set_option",
+    "ti_abi_version", "ti_forest_set_option", "ti_pretransform_device",
 )
 
 # ti_forest_set_option options (include/treeinfer.h)
@@ -81,6 +81,10 @@ class _ForestDesc(ctypes.Structure):
         ("lin_feature", ctypes.c_void_p),
         ("lin_coeff", ctypes.c_void_p),
         ("lin_const", ctypes.c_void_p),
+        ("n_pre_steps", ctypes.c_int32),
+        ("reserved1", ctypes.c_int32),
+        ("pre_op", ctypes.c_void_p),
+        ("pre_const", ctypes.c_void_p),
     ]
 
 
@@ -104,6 +108,7 @@ class _ForestInfo(ctypes.Structure):
         ("linear", ctypes.c_int32),
         ("shap_table_bytes", ctypes.c_int64),
         ("shap_table_build_ms", ctypes.c_double),
+        ("pre_steps", ctypes.c_int32),
     ]
 
 
@@ -146,6 +151,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.ti_forest_set_option.argtypes = [vp, i32, i64]
         lib.ti_transform_device.restype = ctypes.c_int
         lib.ti_transform_device.argtypes = [vp, i32, vp, i64, vp, i64, vp]
+        lib.ti_pretransform_device.restype = ctypes.c_int
+        lib.ti_pretransform_device.argtypes = [vp, i32, vp, i32, i64, i32, i64, vp, vp]
         if lib.ti_abi_version() != ABI_VERSION:
             raise TreeInferError(-1, f"ABI mismatch: library {lib.ti_abi_version()}, "
                                      f"binding {ABI_VERSION}")
@@ -179,7 +186,9 @@ def prepare_input(forest: Forest, X) -> np.ndarray:
     """Convert X the way the library being replaced converts it.
 
     XGBoost's DMatrix and sklearn's check_array make float32; LightGBM
-    keeps float32 input as float32 and reads anything else as float64.
+    keeps float32 input as float32 and reads anything else as float64, and so
+    do sklearn's scalers and imputer (a Pipeline forest: its pre-steps run in
+    the element type the rows arrive in).
     """
     X = np.asarray(X)
     if X.ndim == 1:
@@ -243,6 +252,10 @@ class DeviceForest:
             desc.lin_feature = _ptr(f.lin_feature) if f.lin_feature.size else None
             desc.lin_coeff = _ptr(f.lin_coeff) if f.lin_coeff.size else None
             desc.lin_const = _ptr(f.lin_const)
+        if f.n_pre_steps:
+            desc.n_pre_steps = f.n_pre_steps
+            desc.pre_op = _ptr(f.pre_ops)
+            desc.pre_const = _ptr(f.pre_consts)
         dev_arr = (ctypes.c_int32 * len(devs))(*devs)
         handle = ctypes.c_void_p()
         _check(self._lib, self._lib.ti_forest_create(ctypes.byref(desc), dev_arr, len(devs),
@@ -310,6 +323,33 @@ class DeviceForest:
         (ti_transform_device; the tree-sharded mode's last step)."""
         _check(self._lib, self._lib.ti_transform_device(self._handle, slot, margin_ptr, n_rows,
                                                         out_ptr, out_len, stream or None))
+
+    def pretransform_device(self, x_ptr: int, x_dtype: int, n_rows: int, n_cols: int,
+                            row_stride: int, out_ptr: int, slot: int = 0, stream: int = 0) -> None:
+        """Enqueue the forest's pre-steps over device rows into a dense
+        float32 [n_rows, n_cols] device array (ti_pretransform_device)."""
+        _check(self._lib, self._lib.ti_pretransform_device(self._handle, slot, x_ptr, x_dtype,
+                                                           n_rows, n_cols, row_stride, out_ptr,
+                                                           stream or None))
+
+    def pretransform(self, X) -> np.ndarray:
+        """The float32 rows the forest walks for X: its pre-steps applied on
+        device slot 0 (a forest without pre-steps: the float32 cast).  X goes
+        through :meth:`prepare_input`; this is what
+        ``Pipeline[:-1].transform(X).astype(float32)`` returns."""
+        import torch
+        X = self.prepare_input(X)
+        rows, cols = X.shape
+        if rows == 0:
+            return np.empty((0, cols), dtype=np.float32)
+        dev = torch.device("cuda", self.devices[0])
+        x = torch.from_numpy(X).to(dev)
+        out = torch.empty((rows, cols), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)      # the library enqueues on its own default stream
+        self.pretransform_device(x.data_ptr(), TI_F32 if X.dtype == np.float32 else TI_F64, rows,
+                                 cols, cols, out.data_ptr())
+        torch.cuda.synchronize(dev)
+        return out.cpu().numpy()
 
     def close(self) -> None:
         if getattr(self, "_handle", None) is not None and self._handle.value:

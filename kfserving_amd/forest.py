@@ -48,6 +48,14 @@ OUT_CONTRIB = 3     # TreeSHAP contributions [rows, K * (F + 1)], bias last per 
 OUT_INTERACT = 4    # SHAP interaction values [rows, K * (F + 1) * (F + 1)] (pred_interactions)
 OUT_CONTRIB_APPROX = 5   # approximate (Saabas) contributions, laid out as OUT_CONTRIB (approx_contribs)
 
+# pre-step operations (treeinfer.h TI_PRE_*)
+PRE_FILL_NAN = 0
+PRE_SUB = 1
+PRE_DIV = 2
+PRE_MUL = 3
+PRE_ADD = 4
+PRE_MAX_STEPS = 16
+
 # LightGBM missing types (decision_type bits 2-3)
 MISSING_NONE = 0
 MISSING_ZERO = 1
@@ -106,6 +114,13 @@ class Forest:
     lin_feature: Optional[np.ndarray] = None    # int32 [M]
     lin_coeff: Optional[np.ndarray] = None      # float64 [M]
     lin_const: Optional[np.ndarray] = None      # float64 [N]
+    # pre-steps (a sklearn Pipeline's scalers and imputer): step s maps element
+    # v of column f with pre_consts[s, f] before any split reads it -- fill NaN,
+    # or one float64 operation rounded to the input's element type; the result
+    # is cast to float32 and walked (include/treeinfer.h).  Both None when the
+    # forest has none
+    pre_ops: Optional[np.ndarray] = None        # int32 [S]
+    pre_consts: Optional[np.ndarray] = None     # float64 [S, F]
     library: str = ""
     objective: str = ""
     feature_names: Optional[List[str]] = None
@@ -122,6 +137,22 @@ class Forest:
     @property
     def has_linear(self) -> bool:
         return self.lin_offset is not None
+
+    @property
+    def n_pre_steps(self) -> int:
+        return 0 if self.pre_ops is None else int(self.pre_ops.shape[0])
+
+    def pre_step_host(self, X: np.ndarray, s: int) -> np.ndarray:
+        """Pre-step ``s`` on a float32 or float64 [rows, F] array, in numpy:
+        the float64 operation rounded to X's element type (numpy computes
+        ``float32 op float64`` in double).  For the handful of rows a plugin
+        checks on the host; batches are transformed on the device."""
+        op, c = int(self.pre_ops[s]), self.pre_consts[s]
+        if op == PRE_FILL_NAN:
+            return np.where(np.isnan(X), c.astype(X.dtype), X)
+        w = X.astype(np.float64)
+        w = w - c if op == PRE_SUB else w / c if op == PRE_DIV else w * c if op == PRE_MUL else w + c
+        return w.astype(X.dtype)
 
     def tree_slice(self, t: int) -> slice:
         return slice(int(self.tree_offset[t]), int(self.tree_offset[t + 1]))
@@ -181,6 +212,16 @@ class Forest:
             if np.any(self.cat_offset[cat] < 0) or np.any(end > self.cat_bits.shape[0]):
                 raise ValueError("categorical bitset out of range")
 
+        if (self.pre_ops is None) != (self.pre_consts is None):
+            raise ValueError("pre-steps need pre_ops and pre_consts")
+        if self.pre_ops is not None:
+            S = self.pre_ops.shape[0]
+            if self.pre_ops.ndim != 1 or np.shape(self.pre_consts) != (S, self.n_features):
+                raise ValueError("pre_consts must be [len(pre_ops), n_features]")
+            # the step count and the op codes are the library's to judge (ti_forest_create)
+            if self.lin_offset is not None:
+                raise ValueError("pre-steps with linear leaves are not supported")
+
         lin = (self.lin_offset, self.lin_feature, self.lin_coeff, self.lin_const)
         if any(a is not None for a in lin):
             if any(a is None for a in lin):
@@ -229,12 +270,16 @@ class Forest:
             self.lin_feature = np.ascontiguousarray(self.lin_feature, dtype=np.int32)
             self.lin_coeff = np.ascontiguousarray(self.lin_coeff, dtype=np.float64)
             self.lin_const = np.ascontiguousarray(self.lin_const, dtype=np.float64)
+        if self.pre_ops is not None:
+            self.pre_ops = np.ascontiguousarray(self.pre_ops, dtype=np.int32)
+            self.pre_consts = np.ascontiguousarray(self.pre_consts, dtype=np.float64)
         return self
 
     def tree_subset(self, t0: int, t1: int, keep_base: bool = True) -> "Forest":
         """Trees [t0, t1) as a forest of their own (same features, groups,
         transform and divisor); base margin zeroed unless ``keep_base`` -- one
-        rank's shard in the tree-sharded mode (tree_shard.py)."""
+        rank's shard in the tree-sharded mode (tree_shard.py).  Pre-steps stay
+        with every subset: each rank transforms its own rows."""
         import dataclasses
         if not (0 <= t0 < t1 <= self.n_trees):
             raise ValueError(f"bad tree range [{t0}, {t1}) of {self.n_trees}")

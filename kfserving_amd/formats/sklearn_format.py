@@ -6,7 +6,9 @@ python/sklearnserver/sklearnserver/model.py:38 (``joblib.load``) and calls at
 RandomForest{Regressor,Classifier}, ExtraTrees{Regressor,Classifier} with one
 output, GradientBoosting{Regressor,Classifier} (forest_from_gradient_boosting)
 and HistGradientBoosting{Regressor,Classifier}
-(forest_from_hist_gradient_boosting).
+(forest_from_hist_gradient_boosting), and a Pipeline of SimpleImputer /
+StandardScaler / MinMaxScaler / MaxAbsScaler / RobustScaler steps in front of
+any of these but HistGradientBoosting (forest_from_pipeline).
 
 Predict semantics encoded (installed sklearn 1.7.2,
 sklearn/tree/_tree.pyx:979-997 and sklearn/ensemble/_forest.py:723-736,
@@ -28,8 +30,9 @@ from typing import Tuple
 
 import numpy as np
 
-from ..forest import (Forest, NODE_NAN_LEFT, TI_F32, TI_F64, T_ARGMAX, T_EXP, T_HINGE, T_IDENTITY,
-                      T_STEP, concat_trees)
+from ..forest import (Forest, NODE_NAN_LEFT, PRE_ADD, PRE_DIV, PRE_FILL_NAN, PRE_MAX_STEPS, PRE_MUL,
+                      PRE_SUB, TI_F32, TI_F64, T_ARGMAX, T_EXP, T_HINGE, T_IDENTITY, T_STEP,
+                      concat_trees)
 
 TREE_LEAF = -1
 
@@ -347,8 +350,123 @@ def forest_from_hist_gradient_boosting(est) -> Forest:
     ).contiguous()
 
 
+def _pipeline_step_ops(name: str, step, F: int) -> list:
+    """(op, constants [F]) of one fitted Pipeline step, in the order the
+    installed sklearn 1.7.2 applies them in ``transform`` (in place, on a copy
+    of X in X's own float type):
+
+        SimpleImputer   (impute/_base.py)       X[isnan(X)] = statistics_
+        StandardScaler  (preprocessing/_data.py) X -= mean_ ; X /= scale_
+        MinMaxScaler                             X *= scale_ ; X += min_
+        MaxAbsScaler                             X /= scale_
+        RobustScaler                             X -= center_ ; X /= scale_
+
+    Anything the per-column op chain cannot restate is a TypeError naming the
+    step."""
+    cls = type(step).__name__
+    where = f"Pipeline step '{name}' ({cls})"
+
+    def const(a, what):
+        a = np.asarray(a, dtype=np.float64)
+        if a.shape != (F,):
+            raise TypeError(f"{where}: {what} has shape {a.shape}, expected ({F},)")
+        return a
+
+    if getattr(step, "n_features_in_", F) != F:
+        raise TypeError(f"{where} was fitted on {step.n_features_in_} columns, the final "
+                        f"estimator on {F}")
+    if cls == "SimpleImputer":
+        mv = step.missing_values
+        if not (isinstance(mv, float) and mv != mv):
+            raise TypeError(f"{where}: missing_values={mv!r} is not supported (NaN only)")
+        if step.add_indicator:
+            raise TypeError(f"{where}: add_indicator=True adds columns and is not supported")
+        stats = np.asarray(step.statistics_)
+        if stats.dtype.kind not in "fiu" or stats.shape != (F,) or \
+                not np.all(np.isfinite(stats.astype(np.float64))):
+            raise TypeError(f"{where}: statistics_ must be {F} finite numbers (an imputer that "
+                            "drops an all-missing column changes the column count)")
+        return [(PRE_FILL_NAN, const(stats, "statistics_"))]
+    if cls == "StandardScaler":
+        ops = []
+        if step.with_mean:
+            ops.append((PRE_SUB, const(step.mean_, "mean_")))
+        if step.with_std:
+            ops.append((PRE_DIV, const(step.scale_, "scale_")))
+        return ops
+    if cls == "MinMaxScaler":
+        if step.clip:
+            raise TypeError(f"{where}: clip=True is not supported")
+        return [(PRE_MUL, const(step.scale_, "scale_")), (PRE_ADD, const(step.min_, "min_"))]
+    if cls == "MaxAbsScaler":
+        return [(PRE_DIV, const(step.scale_, "scale_"))]
+    if cls == "RobustScaler":
+        ops = []
+        if step.with_centering:
+            ops.append((PRE_SUB, const(step.center_, "center_")))
+        if step.with_scaling:
+            ops.append((PRE_DIV, const(step.scale_, "scale_")))
+        return ops
+    raise TypeError(f"{where} is not a supported transformer (SimpleImputer / StandardScaler / "
+                    "MinMaxScaler / MaxAbsScaler / RobustScaler)")
+
+
+def forest_from_pipeline(pipe) -> Forest:
+    """A fitted ``sklearn.pipeline.Pipeline`` of imputer / scaler steps in front
+    of a tree ensemble this module flattens (HistGradientBoosting excepted):
+    the final estimator's forest with the steps attached as pre-steps
+    (include/treeinfer.h), which the engine applies on the device where X
+    enters.  ``None`` / ``"passthrough"`` steps are skipped.
+
+    The scalers keep float64 rows as float64 and float32 rows as float32 and
+    work in that type, so the forest declares ``input_dtype`` TI_F64
+    (prepare_input then keeps both) and each pre-step rounds to the element
+    type; the final estimator's own float32 cast is the pre-pass's last
+    conversion.  ``meta["validator"]`` names the first real step: it is the one
+    whose width check answers a request of the wrong shape."""
+    steps = list(pipe.steps)
+    if not steps:
+        raise TypeError("Pipeline has no steps")
+    last_name, last = steps[-1]
+    lcls = type(last).__name__
+    if last is None or isinstance(last, str):
+        raise TypeError(f"Pipeline final step '{last_name}' is {last!r}, not an estimator")
+    if lcls == "Pipeline":
+        raise TypeError(f"Pipeline final step '{last_name}' (Pipeline): nested pipelines are not "
+                        "supported")
+    if lcls in _HGB_NAMES:
+        raise TypeError(f"Pipeline final step '{last_name}' ({lcls}): HistGradientBoosting keeps "
+                        "float64 input and is not supported behind pipeline steps")
+    try:
+        forest = forest_from_sklearn(last)
+    except TypeError as e:
+        raise TypeError(f"Pipeline final step '{last_name}' ({lcls}): {e}") from e
+    F = forest.n_features
+    ops, first = [], None
+    for name, step in steps[:-1]:
+        if step is None or (isinstance(step, str) and step == "passthrough"):
+            continue
+        if first is None:
+            first = type(step).__name__
+        ops += _pipeline_step_ops(name, step, F)
+    if len(ops) > PRE_MAX_STEPS:
+        raise TypeError(f"Pipeline flattens to {len(ops)} per-column operations, at most "
+                        f"{PRE_MAX_STEPS} are supported")
+    if ops:
+        forest.pre_ops = np.asarray([o for o, _ in ops], dtype=np.int32)
+        forest.pre_consts = np.stack([c for _, c in ops])
+        forest.input_dtype = TI_F64
+    # no real step: the final estimator's own float32 cast is all there is
+    forest.meta["pipeline"] = True
+    forest.meta["validator"] = first if first is not None else forest.objective
+    forest.meta["imputes"] = any(o == PRE_FILL_NAN for o, _ in ops)
+    return forest.contiguous()
+
+
 def forest_from_sklearn(est) -> Forest:
-    """Flatten a fitted sklearn tree ensemble."""
+    """Flatten a fitted sklearn tree ensemble, or a Pipeline that ends in one."""
+    if type(est).__name__ == "Pipeline":
+        return forest_from_pipeline(est)
     if type(est).__name__ in _HGB_NAMES:
         return forest_from_hist_gradient_boosting(est)
     if type(est).__name__ in ("GradientBoostingRegressor", "GradientBoostingClassifier"):

@@ -5,7 +5,9 @@ finds model.joblib / .pkl / .pickle like the reference (:21-41; these files
 are the user's own model, loaded with joblib exactly as the reference does)
 or the pickle-free ``model.npz`` tree-array export, and flattens a
 RandomForest / ExtraTrees / DecisionTree / GradientBoosting /
-HistGradientBoosting estimator; ``predict`` runs the trees through
+HistGradientBoosting estimator, or a Pipeline of imputer / scaler steps in
+front of one (its steps run on the device as the forest's pre-steps);
+``predict`` runs the trees through
 libtreeinfer where the reference called ``_model.predict``.
 """
 import os
@@ -58,6 +60,8 @@ class SKLearnModel(GPUForestMixin, KFModel):  # pylint:disable=c-extension-no-me
     def request_matrix(self, request: Dict) -> np.ndarray:
         """sklearn's validate_data checks on the ``instances`` array."""
         f = self._forest
+        if f.meta.get("pipeline"):
+            return self._pipeline_matrix(self._array(request))
         X = np.asarray(self._array(request), dtype=np.float64)
         if f.meta.get("hist_gradient_boosting"):
             return self._hgb_matrix(X)
@@ -75,6 +79,65 @@ class SKLearnModel(GPUForestMixin, KFModel):  # pylint:disable=c-extension-no-me
         if np.isinf(X32).any():
             raise ValueError("Input X contains infinity or a value too large for "
                              "dtype('float32').")
+        return X
+
+    def _pipeline_matrix(self, X: np.ndarray) -> np.ndarray:
+        """``Pipeline.predict``'s checks, in the order its steps make them.
+        The first real step validates the array: float32 stays float32,
+        anything else becomes float64; it must be 2-D, free of infinity (NaN
+        passes the scalers and the imputer) and of the fitted width, and the
+        step's name is in the width message.  The final estimator then casts
+        to float32 and checks again: NaN reaches it only when no imputer
+        precedes it and is refused by GradientBoosting; a value the steps push
+        beyond float32 is refused as too large.  That last check does not
+        transform the batch: every pre-step is monotone in the value and
+        rounding keeps that, so a column's transformed extremes come from its
+        finite minimum and maximum (and the imputer's fill), and the op chain
+        runs on those 3 x F values alone."""
+        f = self._forest
+        who, F = f.meta["validator"], f.n_features
+        X = np.asarray(X)
+        if X.dtype != np.float32:
+            X = np.asarray(X, dtype=np.float64)
+        if X.ndim < 2:      # check_array's text: the first line, then the array and the advice
+            raise ValueError("Expected 2D array, got %s array instead:\narray=%s.\n"
+                             "Reshape your data either using array.reshape(-1, 1) if your data "
+                             "has a single feature or array.reshape(1, -1) if it contains a "
+                             "single sample." % ("1D" if X.ndim else "scalar", X))
+        if X.ndim > 2:
+            raise ValueError("Found array with dim %d, while dim <= 2 is required by %s."
+                             % (X.ndim, who))
+        if np.isinf(X).any():
+            raise ValueError("Input X contains infinity or a value too large for dtype('%s')."
+                             % X.dtype.name)
+        if X.shape[1] != F:
+            raise ValueError("X has %d features, but %s is expecting %d features as input."
+                             % (X.shape[1], who, F))
+        nan = np.isnan(X)
+        has_nan = bool(nan.any())
+        if has_nan and not f.meta.get("imputes") and not f.meta.get("allow_nan", True):
+            raise ValueError("Input X contains NaN.")   # the final estimator's validate_data
+        if X.shape[0] == 0:
+            return X
+        if has_nan:
+            lo = np.where(nan, np.inf, X).min(axis=0)
+            hi = np.where(nan, -np.inf, X).max(axis=0)
+            lo[np.isinf(lo)] = np.nan        # a column of NaN alone
+            hi[np.isinf(hi)] = np.nan
+        else:
+            lo, hi = X.min(axis=0), X.max(axis=0)
+        E = np.stack([lo, hi, np.full(F, np.nan, dtype=X.dtype)]).astype(X.dtype)
+        if f.n_pre_steps:
+            with np.errstate(all="ignore"):
+                for s in range(f.n_pre_steps):
+                    E = f.pre_step_host(E, s)
+                    if np.isinf(E).any():    # the next step's own check_array
+                        raise ValueError("Input X contains infinity or a value too large for "
+                                         "dtype('%s')." % X.dtype.name)
+        with np.errstate(over="ignore"):
+            if np.isinf(E.astype(np.float32)).any():
+                raise ValueError("Input X contains infinity or a value too large for "
+                                 "dtype('float32').")
         return X
 
     def _hgb_matrix(self, X: np.ndarray) -> np.ndarray:
@@ -132,8 +195,8 @@ class SKLearnModel(GPUForestMixin, KFModel):  # pylint:disable=c-extension-no-me
         float64 rule has not been held against _hgb_matrix on an
         ``instances`` route even for models without categorical features."""
         f = self._forest
-        if f is None or f.meta.get("hist_gradient_boosting"):
-            return None
+        if f is None or f.meta.get("hist_gradient_boosting") or f.meta.get("pipeline"):
+            return None   # a Pipeline's checks (_pipeline_matrix) are the application's too
         return (1 << 8) | (0 if f.meta.get("allow_nan", True) else (1 << 9))
 
     @property
