@@ -915,6 +915,9 @@ void ensure_shap_table(ti_forest* f, DeviceForest& d) {
   if (ok) mem.ptrs.push_back(d.shap_tab);
   if (ok) {
     const unsigned np = static_cast<unsigned>(f->h_tab_off.size());
+    // an error that an earlier call left on this thread (the caller's own,
+    // say) is not this launch's: it must not cost the replica its table
+    (void)hipGetLastError();
     if (f->shap_tab_mt == 4)
       hipLaunchKernelGGL((shap_table_kernel<float, 16>), dim3(np), dim3(256), 0, s,
                          d.shap_paths, d.shap_elems, d.shap_tab_off, static_cast<float*>(d.shap_tab));

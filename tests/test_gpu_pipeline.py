@@ -3,13 +3,14 @@ chunks alternate between two streams with bounded pinned buffers
 (treeinfer.hip predict_pipelined).  TI_CHUNK_MB=1 makes a 50,003-row C2-shaped
 batch six chunks, the last one ragged; results are bit-exact against the C
 port and against one device-resident launch."""
+import ctypes
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from kfserving_amd.engine import OPT_HOST_REGISTER, DeviceForest
+from kfserving_amd.engine import OPT_HOST_REGISTER, DeviceForest, load_library
 from kfserving_amd.formats.xgboost_format import forest_from_raw_trees, synthetic_complete_trees
 from kfserving_amd.forest import OUT_LEAF, OUT_MARGIN, OUT_PREDICT, TI_F32
 from oracle import port
@@ -79,19 +80,57 @@ def test_registered_host_predict_bit_exact(small_chunks, strided):
     assert np.array_equal(leaf, dev.predict(np.ascontiguousarray(X), OUT_LEAF))
 
 
-def test_registered_host_predict_multi_device_and_already_registered(small_chunks):
+def _host_register_works():
+    """Whether the HIP runtime can page-lock memory the program already holds
+    (hipHostRegister); a virtual machine may not let it.  Asked of the runtime
+    libtreeinfer.so itself is linked to, and the error a refusal leaves on the
+    thread is taken off, so that no later launch reports it."""
+    lib = load_library()
+    lib.hipHostRegister.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint]
+    buf = np.zeros(2 * 4096, dtype=np.uint8)
+    page = (buf.ctypes.data + 4095) & ~4095
+    if lib.hipHostRegister(page, 4096, 0) != 0:
+        lib.hipGetLastError()
+        return False
+    lib.hipHostUnregister.argtypes = [ctypes.c_void_p]
+    assert lib.hipHostUnregister(page) == 0
+    return True
+
+
+@pytest.fixture(scope="module")
+def three_slot_case():
+    """A forest for three device slots, its batch (20,371 rows a slot: > 2
+    chunks each, ragged) and the C port's margins; read only."""
+    trees, ti = synthetic_complete_trees(60, 8, 28, seed=8)
+    f = forest_from_raw_trees(trees, ti, 28, 0, 0.0, "binary:logistic")
+    X = np.random.default_rng(9).standard_normal((61_111, 28)).astype(np.float32)
+    return f, X, port.xgb_predict(trees, ti, 1, 0.0, 28, X)[:, 0]
+
+
+def test_registered_host_predict_multi_device(small_chunks, three_slot_case):
+    """TI_OPT_HOST_REGISTER=1 with several device slots, whether or not the
+    runtime can page-lock the batch (where it cannot, every shard takes the
+    pinned staging chunks): bit-exact against the C port, twice."""
+    f, X, want = three_slot_case
+    dev = DeviceForest(f, [0, 0, 0])           # three slots: 3 shard threads
+    dev.set_option(OPT_HOST_REGISTER, 1)
+    for _ in range(2):
+        assert np.array_equal(dev.predict(X, OUT_MARGIN), want)
+    dev.close()
+
+
+def test_registered_host_predict_multi_device_and_already_registered(small_chunks, three_slot_case):
     """with several device slots the whole batch is page-locked
     once before the shard threads start (slices sharing boundary pages used
     to register and unregister them per thread); a buffer whose pages are
     already registered by someone else is not used for direct DMA (the
-    pinned staging chunks take it).  Bit-exact against the C port both ways."""
-    trees, ti = synthetic_complete_trees(60, 8, 28, seed=8)
-    f = forest_from_raw_trees(trees, ti, 28, 0, 0.0, "binary:logistic")
+    pinned staging chunks take it).  Bit-exact against the C port both ways.
+    Needs a runtime that can page-lock the test's own buffer."""
+    if not _host_register_works():
+        pytest.skip("hipHostRegister is not supported here")
+    f, X, want = three_slot_case
     dev = DeviceForest(f, [0, 0, 0])           # three slots: 3 shard threads
     dev.set_option(OPT_HOST_REGISTER, 1)
-    rows = 61_111                              # 20,371 a slot: > 2 chunks each, ragged
-    X = np.random.default_rng(9).standard_normal((rows, 28)).astype(np.float32)
-    want = port.xgb_predict(trees, ti, 1, 0.0, 28, X)[:, 0]
     for _ in range(2):
         assert np.array_equal(dev.predict(X, OUT_MARGIN), want)
     # X registered by another owner for the duration: the call must not rely

@@ -145,6 +145,26 @@ def test_table_failure_falls_back_to_arithmetic(how, monkeypatch):
     assert np.array_equal(dev.predict(X, OUT_CONTRIB), want)    # still served, no retry
 
 
+def test_table_built_despite_stale_runtime_error():
+    """An error that a failed runtime call of the caller's own left on the
+    thread (here hipSetDevice(-1)) is not the table build's launch failure:
+    the table is built all the same, and serves the arithmetic kernel's
+    contributions."""
+    f = _xgb(40, 6, 12, seed=23)
+    X = _rows(f, 300, seed=24)
+    ref = DeviceForest(f, [0])
+    ref.set_option(OPT_SHAP_TABLE_ROWS, 0)
+    want = ref.predict(X, OUT_CONTRIB)
+    dev = DeviceForest(f, [0])
+    try:
+        assert dev._lib.hipSetDevice(-1) != 0
+        got = dev.predict(X, OUT_CONTRIB)
+    finally:
+        dev._lib.hipGetLastError()
+    assert dev.info()["shap_table"] == 1
+    assert np.array_equal(got, want)
+
+
 def test_set_option_rejects_bad_values():
     dev = DeviceForest(_xgb(4, 3, 5, seed=9), [0])
     with pytest.raises(TreeInferError, match="unknown option"):
