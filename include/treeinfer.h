@@ -114,7 +114,7 @@
 extern "C" {
 #endif
 
-#define TI_ABI_VERSION 9
+#define TI_ABI_VERSION 10
 
 /* return codes */
 #define TI_OK               0
@@ -206,6 +206,28 @@ extern "C" {
                               /* F, K, depth and path length do not restrict it. */
                               /* The host pipeline sizes its row chunks by this  */
                               /* kind's output row.                              */
+#define TI_OUTPUT_CONTRIB_INTERV 6
+                              /* ABI 10: interventional TreeSHAP against the     */
+                              /* background set of ti_forest_set_background      */
+                              /* (shap.TreeExplainer(model, data)), [rows, K *   */
+                              /* (F + 1)] laid out, typed and divided exactly as */
+                              /* TI_OUTPUT_CONTRIB.  With f the margin and z the */
+                              /* B background rows, column i of a group is       */
+                              /*   sum_S w(S) mean_z [f(x_{S+i}, z_rest) -       */
+                              /*                      f(x_S, z_rest)],           */
+                              /* the Shapley value of feature i in the game that */
+                              /* takes the features of S from x and the rest     */
+                              /* from z; the bias column is mean_z f(z), so a    */
+                              /* group's columns sum to its margin.  Float64     */
+                              /* arithmetic in a fixed order: two calls give the */
+                              /* same bits.  It reads no cover, so forests       */
+                              /* without covers are served.  TI_ERR_INVALID with */
+                              /* no background set; TI_ERR_UNSUPPORTED for a     */
+                              /* forest with a TI_NODE_CAT_XGB node, with linear */
+                              /* leaves, with pre-steps (neither Z nor X goes    */
+                              /* through the pre-pass for this kind), with K *   */
+                              /* (F + 1) > 128 or with a root-to-leaf path of    */
+                              /* more than 32 distinct features.                 */
 
 /*
  * Canonical forest: host structure-of-arrays over the nodes of all trees,
@@ -344,6 +366,21 @@ int ti_forest_create(const ti_forest_desc* desc, const int32_t* devices,
 int ti_forest_destroy(ti_forest* forest);
 
 int ti_forest_get_info(const ti_forest* forest, ti_forest_info* info);
+
+/* ABI 10: the background set of TI_OUTPUT_CONTRIB_INTERV.  Z: host rows
+ * [n_rows, n_cols] with row_stride elements between rows, element type z_dtype
+ * (TI_F32 / TI_F64), read as ti_predict reads X (lgb_zero_map included) and
+ * not kept after the call.  Replaces any earlier background; n_rows == 0
+ * clears it.  Like ti_forest_destroy, it must be called with no other call in
+ * flight on the forest.  The first call builds the TreeSHAP path tables; each
+ * call builds, on every device, a table of 4 bytes per (root-to-leaf path,
+ * background row), which ti_forest_info.device_bytes counts, and the bias: the
+ * forest's TI_OUTPUT_MARGIN over Z, summed in float64 in row order, over
+ * n_rows.  TI_ERR_UNSUPPORTED for the forests TI_OUTPUT_CONTRIB_INTERV refuses
+ * and for a table above 1 GiB per device; the forest then has no background.
+ * Replaces the `data` argument of shap.TreeExplainer(model, data). */
+int ti_forest_set_background(ti_forest* forest, const void* Z, int32_t z_dtype,
+                             int64_t n_rows, int32_t n_cols, int64_t row_stride);
 
 /* Per-forest tuning that changes speed, never results (both TreeSHAP kernels
  * produce the same contributions).  0 or TI_ERR_INVALID for an unknown option

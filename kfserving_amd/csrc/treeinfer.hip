@@ -20,6 +20,7 @@
 #include "treeinfer_forest.h"
 #include "treeinfer_pack.h"
 #include "treeinfer_shap.h"
+#include "treeinfer_shap_interv.h"
 #include "treeinfer_approx.h"
 #include "treeinfer_pre.h"
 
@@ -47,6 +48,7 @@ void free_device(DeviceForest& d) {
   d.forest_mem.release();
   static_cast<ForestPtrs&>(d) = ForestPtrs();
   free_shap(d);
+  free_interv(d);
   free_approx(d);
   free_scratch(d);
   if (d.interact_done) (void)hipEventDestroy(d.interact_done);
@@ -188,7 +190,7 @@ void occ_note(KernelFn fn, int block, size_t lds) {
 
 int64_t output_width(const ti_forest* f, int kind) {
   if (kind == TI_OUTPUT_LEAF) return f->T;
-  if (kind == TI_OUTPUT_CONTRIB || kind == TI_OUTPUT_CONTRIB_APPROX)
+  if (kind == TI_OUTPUT_CONTRIB || kind == TI_OUTPUT_CONTRIB_APPROX || kind == TI_OUTPUT_CONTRIB_INTERV)
     return static_cast<int64_t>(f->K) * (f->F + 1);
   if (kind == TI_OUTPUT_INTERACT) return static_cast<int64_t>(f->K) * (f->F + 1) * (f->F + 1);
   if (kind == TI_OUTPUT_PREDICT && f->transform == TI_TRANSFORM_ARGMAX) return 1;
@@ -838,7 +840,10 @@ int launch_chunked(ti_forest* f, int slot, const void* X, int xdt, int64_t rows,
     }
     return TI_OK;
   }
-  const int64_t cw = kind == TI_OUTPUT_CONTRIB ? f->F + 1 : 1;   // columns per group
+  // TI_OUTPUT_CONTRIB_INTERV: each part holds the background's masks for its own
+  // paths and writes its groups' columns, as TI_OUTPUT_CONTRIB does
+  const bool contrib = kind == TI_OUTPUT_CONTRIB || kind == TI_OUTPUT_CONTRIB_INTERV;
+  const int64_t cw = contrib ? f->F + 1 : 1;   // columns per group
   for (auto& p : f->parts)
     tmp_bytes = std::max(tmp_bytes, static_cast<size_t>(rows) *
                                         (kind == TI_OUTPUT_LEAF ? 4 * p->T : as * p->K * cw));
@@ -870,7 +875,7 @@ int launch_chunked(ti_forest* f, int slot, const void* X, int xdt, int64_t rows,
                          dim3(threads), 0, stream, static_cast<const int32_t*>(tmp), rows, p->T,
                          dmap, f->T, static_cast<int32_t*>(out));
     } else {
-      const int pk = kind == TI_OUTPUT_CONTRIB ? TI_OUTPUT_CONTRIB : TI_OUTPUT_MARGIN;
+      const int pk = contrib ? kind : TI_OUTPUT_MARGIN;
       rc = launch_any(p, slot, X, xdt, rows, cols, stride, pk, tmp, stream);
       if (rc) break;
       if (hipMemcpy2DAsync(static_cast<unsigned char*>(mdst) + f->part_k0[c] * cw * as,
@@ -1063,6 +1068,14 @@ int launch_walk(ti_forest* f, int slot, const void* X, int xdt, int64_t rows, in
     return fail(TI_ERR_UNSUPPORTED,
                 "TI_OUTPUT_INTERACT of a forest with linear leaves (contributions of a linear-tree "
                 "model are refused too)");
+  if (kind == TI_OUTPUT_CONTRIB_INTERV) {
+    // a forest in group parts answers for itself first: its parts hold no
+    // pre-steps and fewer groups
+    const int rc = interv_refusal(f);
+    if (rc) return rc;
+    if (f->parts.empty())
+      return launch_interv(f, *f->devs[slot], X, xdt, rows, cols, stride, out, stream);
+  }
   if (kind == TI_OUTPUT_CONTRIB && f->parts.empty())
     return launch_contrib(f, *f->devs[slot], X, xdt, rows, cols, stride, out, stream);
   if (kind == TI_OUTPUT_INTERACT && f->parts.empty())
@@ -1283,6 +1296,46 @@ int ti_forest_destroy(ti_forest* forest) {
   return TI_OK;
 }
 
+int ti_forest_set_background(ti_forest* f, const void* Z, int32_t zdt, int64_t B, int32_t cols,
+                             int64_t stride) {
+  if (!f) return fail(TI_ERR_INVALID, "null forest");
+  if (zdt != TI_F32 && zdt != TI_F64) return fail(TI_ERR_INVALID, "z_dtype must be TI_F32 or TI_F64");
+  if (B < 0) return fail(TI_ERR_INVALID, "negative n_rows");
+  if (B > 0 && !Z) return fail(TI_ERR_INVALID, "null data pointer");
+  if (B > 0 && cols <= 0) return fail(TI_ERR_INVALID, "n_cols must be > 0");
+  if (B > 0 && stride < cols) return fail(TI_ERR_INVALID, "row_stride < n_cols");
+  // the earlier background goes first, whatever becomes of the new one
+  for (auto& p : f->parts) clear_background(p.get());
+  clear_background(f);
+  if (B == 0) return TI_OK;
+  int rc = interv_refusal(f);
+  if (rc) return rc;
+  for (auto& p : f->parts) {   // each group part keeps the masks of its own paths
+    if ((rc = ti_forest_set_background(p.get(), Z, zdt, B, cols, stride))) {
+      const std::string err = g_last_error;
+      for (auto& q : f->parts) clear_background(q.get());
+      return fail(rc, err);
+    }
+  }
+  if (!f->parts.empty()) {
+    f->interv_B = B;
+    return TI_OK;
+  }
+  // the bias: the forest's own margins of Z, summed in float64 in row order
+  const int K = f->K;
+  std::vector<double> bias(K, 0.0);
+  {
+    std::vector<unsigned char> m(static_cast<size_t>(B) * K * dtype_size(f->accum));
+    if ((rc = ti_predict(f, Z, zdt, B, cols, stride, TI_OUTPUT_MARGIN, m.data(), B * K))) return rc;
+    for (int64_t r = 0; r < B; ++r)
+      for (int k = 0; k < K; ++k)
+        bias[k] += f->accum == TI_F64 ? reinterpret_cast<const double*>(m.data())[r * K + k]
+                                      : static_cast<double>(reinterpret_cast<const float*>(m.data())[r * K + k]);
+    for (int k = 0; k < K; ++k) bias[k] /= static_cast<double>(B);
+  }
+  return set_background(f, Z, zdt, B, cols, stride, bias);
+}
+
 int ti_forest_get_info(const ti_forest* f, ti_forest_info* info) {
   if (!f || !info) return fail(TI_ERR_INVALID, "null argument");
   info->layout = f->layout;
@@ -1358,7 +1411,7 @@ int ti_forest_set_option(ti_forest* f, int32_t option, int64_t value) {
 int ti_output_shape(const ti_forest* f, int32_t kind, int64_t n_rows, int64_t* out_len,
                     int32_t* out_dtype) {
   if (!f || !out_len || !out_dtype) return fail(TI_ERR_INVALID, "null argument");
-  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_CONTRIB_APPROX) return fail(TI_ERR_INVALID, "bad output kind");
+  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_CONTRIB_INTERV) return fail(TI_ERR_INVALID, "bad output kind");
   if (n_rows < 0) return fail(TI_ERR_INVALID, "negative n_rows");
   *out_len = n_rows * output_width(f, kind);
   *out_dtype = output_dtype(f, kind);
@@ -1369,7 +1422,7 @@ static int check_call(const ti_forest* f, const void* X, int32_t xdt, int64_t ro
                       int64_t stride, int32_t kind, const void* out, int64_t out_len) {
   if (!f) return fail(TI_ERR_INVALID, "null forest");
   if (xdt != TI_F32 && xdt != TI_F64) return fail(TI_ERR_INVALID, "x_dtype must be TI_F32 or TI_F64");
-  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_CONTRIB_APPROX) return fail(TI_ERR_INVALID, "bad output kind");
+  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_CONTRIB_INTERV) return fail(TI_ERR_INVALID, "bad output kind");
   if (rows < 0) return fail(TI_ERR_INVALID, "negative n_rows");
   if (rows == 0) return TI_OK;
   if (!X || !out) return fail(TI_ERR_INVALID, "null data pointer");

@@ -352,6 +352,13 @@ struct DeviceForest : ForestPtrs, ShapPtrs, ApproxPtrs, ScratchBufs {
   size_t interact_cap = 0;
   hipEvent_t interact_done = nullptr;
   CallScratch scratch;
+  // TI_OUTPUT_CONTRIB_INTERV (treeinfer_shap_interv.h): the background's mask
+  // table [paths][B], its mean margin [K] and the weight table; counted in
+  // `bytes` as interv_bytes
+  uint32_t* interv_masks = nullptr;
+  double* interv_bias = nullptr;
+  double* interv_weights = nullptr;
+  int64_t interv_bytes = 0;
   int64_t bytes = 0;
   std::mutex mu;
 };
@@ -564,7 +571,9 @@ struct ti_forest {
   // ---- the packed arrays, until every replica is resident
   std::unique_ptr<HostImage> host;
   // TreeSHAP (TI_OUTPUT_CONTRIB); has_shap = 0 when the forest has no covers
-  // (shap_refused = 1) or a categorical node with XGBoost's rule (2).
+  // (shap_refused = 1) or a categorical node with XGBoost's rule (2).  The
+  // path tables of a forest without covers still serve interventional
+  // contributions, which read no cover (every zero fraction is then 1).
   // The path tables are built and uploaded on the first contributions call
   // (ensure_shap), from a host copy of the arrays they need, so predict-only
   // serving never pays for them.
@@ -616,5 +625,9 @@ struct ti_forest {
     std::vector<double> leaf_value, cover, base_margin;
   };
   std::unique_ptr<ApproxSource> approx_src;
+  // Interventional contributions (TI_OUTPUT_CONTRIB_INTERV): rows of the
+  // background set by ti_forest_set_background, 0 for none.  Written with no
+  // call in flight, so calls read it without a lock.
+  int64_t interv_B = 0;
   std::vector<std::unique_ptr<DeviceForest>> devs;
 };

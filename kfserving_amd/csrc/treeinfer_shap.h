@@ -628,9 +628,9 @@ void free_shap(DeviceForest& d) {
   d.shap_tab_state = 0;
 }
 
-// TreeSHAP path tables + bias (see ShapPath).  Forests without covers or
-// with XGBoost-rule categorical splits get none (TI_OUTPUT_CONTRIB is then
-// unsupported).
+// TreeSHAP path tables + bias (see ShapPath).  Forests with XGBoost-rule
+// categorical splits get none; forests without covers get paths with zero
+// fractions of 1 and no bias (TI_OUTPUT_CONTRIB is unsupported for both).
 //
 // The categorical part of an element is a set of codes `allow` (words, bit
 // v % 32 of word v / 32) plus kShapCatOutside, which says what happens to
@@ -710,7 +710,7 @@ struct ShapBuilder {
           break;
         }
       ShapElem& e = el.e;
-      e.zf = (d->cover[b + child] / d->cover[g]) * e.zf;
+      if (d->cover) e.zf = (d->cover[b + child] / d->cover[g]) * e.zf;   // no covers: zf stays 1
       if (cat) {
         // the interval and the NaN / zero flags belong to the numerical splits
         cat_turn(el, d->cat_bits + d->cat_offset[g], static_cast<size_t>(d->cat_nwords[g]), left);
@@ -748,15 +748,18 @@ struct ShapBuilder {
 
 // At create: whether contributions are possible (covers; categorical nodes
 // all with LightGBM's rule), and the host copy build_shap will read on first
-// use.  The element's category set is LightGBM's membership test; a forest
+// use.  A forest without covers keeps the copy too: its paths serve
+// TI_OUTPUT_CONTRIB_INTERV (treeinfer_shap_interv.h), with has_shap = 0 and
+// shap_refused = 1 as before, and zero fractions of 1 that nothing reads.  The element's category set is LightGBM's membership test; a forest
 // with an XGBoost-rule node (TI_NODE_CAT_XGB: in the set -> right, invalid
 // codes left, NaN by flag) is refused.
 void keep_shap_source(const ti_forest_desc* d, ti_forest* f) {
-  f->shap_refused = 1;
-  if (!d->cover) return;
-  f->shap_refused = 2;
-  if (f->has_cat_xgb) return;
-  f->shap_refused = 0;
+  f->shap_refused = d->cover ? 0 : 1;
+  if (f->has_cat_xgb) {
+    if (d->cover) f->shap_refused = 2;
+    return;
+  }
+  // without covers the paths still serve TI_OUTPUT_CONTRIB_INTERV
   auto src = std::make_unique<ti_forest::ShapSource>();
   const int64_t N = d->n_nodes, T = d->n_trees;
   src->tree_offset.assign(d->tree_offset, d->tree_offset + T + 1);
@@ -767,7 +770,7 @@ void keep_shap_source(const ti_forest_desc* d, ti_forest* f) {
   src->threshold.assign(d->threshold, d->threshold + N);
   src->leaf_value.assign(d->leaf_value, d->leaf_value + N * d->leaf_width);
   src->base_margin.assign(d->base_margin, d->base_margin + d->n_groups);
-  src->cover.assign(d->cover, d->cover + N);
+  if (d->cover) src->cover.assign(d->cover, d->cover + N);
   src->flags.assign(d->flags, d->flags + N);
   src->desc = *d;
   src->desc.tree_offset = src->tree_offset.data();
@@ -778,7 +781,7 @@ void keep_shap_source(const ti_forest_desc* d, ti_forest* f) {
   src->desc.threshold = src->threshold.data();
   src->desc.leaf_value = src->leaf_value.data();
   src->desc.base_margin = src->base_margin.data();
-  src->desc.cover = src->cover.data();
+  src->desc.cover = d->cover ? src->cover.data() : nullptr;
   src->desc.flags = src->flags.data();
   src->desc.leaf_id = nullptr;
   src->desc.cat_bits = nullptr;
@@ -793,7 +796,7 @@ void keep_shap_source(const ti_forest_desc* d, ti_forest* f) {
     src->desc.cat_nwords = src->cat_nwords.data();
   }
   f->shap_src = std::move(src);
-  f->has_shap = 1;
+  f->has_shap = d->cover ? 1 : 0;
 }
 
 void build_shap(const ti_forest_desc* d, ti_forest* f) {
@@ -806,6 +809,7 @@ void build_shap(const ti_forest_desc* d, ti_forest* f) {
     sb.group = d->leaf_width == 1 ? d->tree_group[t] : 0;
     sb.cur.clear();
     sb.dfs(0);
+    if (!d->cover) continue;   // no covers: no expected value, and nobody reads the bias
     const std::vector<double> m = sb.mean(0);
     if (d->leaf_width == 1) bias[sb.group] += m[0];
     else for (int k = 0; k < K; ++k) bias[k] += m[k];

@@ -18,10 +18,10 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .forest import (Forest, OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_INTERACT, OUT_LEAF, OUT_MARGIN,
-                     OUT_PREDICT, TI_F32, TI_F64, TI_I32)
+from .forest import (Forest, OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_CONTRIB_INTERV, OUT_INTERACT,
+                     OUT_LEAF, OUT_MARGIN, OUT_PREDICT, TI_F32, TI_F64, TI_I32)
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 _LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("TREEINFER_LIB", os.path.join(_LIB_DIR, "libtreeinfer.so"))
 
@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = (
     "ti_forest_create", "ti_forest_destroy", "ti_forest_get_info", "ti_output_shape",
     "ti_predict", "ti_predict_device", "ti_transform_device", "ti_last_error", "ti_device_count",
     "ti_abi_version", "ti_forest_set_option", "ti_pretransform_device",
+    "ti_forest_set_background",
 )
 
 # ti_forest_set_option options (include/treeinfer.h)
@@ -153,6 +154,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.ti_transform_device.argtypes = [vp, i32, vp, i64, vp, i64, vp]
         lib.ti_pretransform_device.restype = ctypes.c_int
         lib.ti_pretransform_device.argtypes = [vp, i32, vp, i32, i64, i32, i64, vp, vp]
+        lib.ti_forest_set_background.restype = ctypes.c_int
+        lib.ti_forest_set_background.argtypes = [vp, vp, i32, i64, i32, i64]
         if lib.ti_abi_version() != ABI_VERSION:
             raise TreeInferError(-1, f"ABI mismatch: library {lib.ti_abi_version()}, "
                                      f"binding {ABI_VERSION}")
@@ -274,6 +277,19 @@ class DeviceForest:
         OPT_LINEAR_SCRATCH_MB)."""
         _check(self._lib, self._lib.ti_forest_set_option(self._handle, option, int(value)))
 
+    def set_background(self, Z) -> None:
+        """ti_forest_set_background: the reference rows of OUT_CONTRIB_INTERV
+        (``shap.TreeExplainer(model, data)``'s data), converted as
+        :meth:`prepare_input` converts X; NaN is missing.  ``None`` or no rows
+        clears it.  Call it with no predict in flight on this forest."""
+        if Z is None:
+            Z = np.empty((0, max(self.forest.n_features, 1)), dtype=np.float32)
+        Z = self.prepare_input(Z)
+        rows, cols = Z.shape
+        zdt = TI_F32 if Z.dtype == np.float32 else TI_F64
+        _check(self._lib, self._lib.ti_forest_set_background(self._handle, _ptr(Z) if rows else None,
+                                                             zdt, rows, cols, cols))
+
     def linear_tile_rows(self, x_dtype) -> int:
         """Rows per tile of the linear-leaf pass (launch_linear in
         treeinfer.hip) for input of ``x_dtype``: the largest of 256 / 128 / 64
@@ -366,5 +382,5 @@ class DeviceForest:
 __all__ = ["DeviceForest", "TreeInferError", "prepare_input", "load_library", "device_count", "default_devices",
            "OPT_SHAP_TABLE_ROWS", "OPT_SHAP_TABLE_MB", "OPT_HOST_REGISTER", "OPT_LINEAR_SCRATCH_MB",
            "EXPORTED_SYMBOLS", "OUT_MARGIN", "OUT_PREDICT", "OUT_LEAF", "OUT_CONTRIB", "OUT_INTERACT",
-           "OUT_CONTRIB_APPROX",
+           "OUT_CONTRIB_APPROX", "OUT_CONTRIB_INTERV",
            "TI_F32", "TI_F64", "TI_I32"]

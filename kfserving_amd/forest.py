@@ -47,6 +47,7 @@ OUT_LEAF = 2
 OUT_CONTRIB = 3     # TreeSHAP contributions [rows, K * (F + 1)], bias last per group
 OUT_INTERACT = 4    # SHAP interaction values [rows, K * (F + 1) * (F + 1)] (pred_interactions)
 OUT_CONTRIB_APPROX = 5   # approximate (Saabas) contributions, laid out as OUT_CONTRIB (approx_contribs)
+OUT_CONTRIB_INTERV = 6   # interventional TreeSHAP against a background set, laid out as OUT_CONTRIB
 
 # pre-step operations (treeinfer.h TI_PRE_*)
 PRE_FILL_NAN = 0
@@ -310,7 +311,7 @@ class Forest:
     def output_width(self, kind: int) -> int:
         if kind == OUT_LEAF:
             return self.n_trees
-        if kind in (OUT_CONTRIB, OUT_CONTRIB_APPROX):
+        if kind in (OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_CONTRIB_INTERV):
             return self.n_groups * (self.n_features + 1)
         if kind == OUT_INTERACT:
             return self.n_groups * (self.n_features + 1) ** 2

@@ -20,18 +20,22 @@ BOOSTER_FILE = "model.bst"
 
 
 class LightGBMModel(GPUForestMixin, KFModel):
-    def __init__(self, name: str, model_dir: str, nthread: int, booster: Forest = None):
+    def __init__(self, name: str, model_dir: str, nthread: int, booster: Forest = None,
+                 background=None):
         super().__init__(name)
         self.name = name
         self.model_dir = model_dir
         self.nthread = nthread
+        if background is not None:
+            self.set_background(background)
         if booster is not None:
             self._set_forest(booster)
             self.ready = True
 
     def load(self) -> bool:
-        model_file = os.path.join(Storage.download(self.model_dir), BOOSTER_FILE)
-        self._set_forest(load_lightgbm_model(model_file))
+        model_path = Storage.download(self.model_dir)
+        self._set_forest(load_lightgbm_model(os.path.join(model_path, BOOSTER_FILE)))
+        self._load_background(model_path)
         self.ready = True
         return self.ready
 

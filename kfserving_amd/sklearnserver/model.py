@@ -27,11 +27,13 @@ ARRAYS_EXTENSION = ".npz"
 
 
 class SKLearnModel(GPUForestMixin, KFModel):  # pylint:disable=c-extension-no-member
-    def __init__(self, name: str, model_dir: str):
+    def __init__(self, name: str, model_dir: str, background=None):
         super().__init__(name)
         self.name = name
         self.model_dir = model_dir
         self.ready = False
+        if background is not None:
+            self.set_background(background)
 
     def load(self) -> bool:
         model_path = Storage.download(self.model_dir)
@@ -47,6 +49,8 @@ class SKLearnModel(GPUForestMixin, KFModel):  # pylint:disable=c-extension-no-me
             if os.path.exists(npz):
                 self._set_forest(load_tree_arrays(npz))
                 self.ready = True
+        if self.ready:
+            self._load_background(model_path)
         return self.ready
 
     def _array(self, request: Dict) -> np.ndarray:

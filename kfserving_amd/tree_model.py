@@ -9,13 +9,17 @@ library turns a JSON request into a feature matrix.
 """
 from __future__ import annotations
 
+import os
 import threading
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
 from .engine import DeviceForest, prepare_input
-from .forest import OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_INTERACT, OUT_PREDICT, Forest
+from .forest import (OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_CONTRIB_INTERV, OUT_INTERACT, OUT_PREDICT,
+                     Forest)
+
+BACKGROUND_FILE = "background.npy"
 
 
 class GPUForestMixin:
@@ -25,6 +29,25 @@ class GPUForestMixin:
     _forest: Optional[Forest] = None
     _device_forest: Optional[DeviceForest] = None
     devices: Optional[Sequence[int]] = None
+    # the reference rows of interventional explanations ([B, F] float, NaN =
+    # missing): the constructor's ``background=`` or background.npy beside the
+    # model file; set on the device forest when it is created
+    _background: Optional[np.ndarray] = None
+
+    def set_background(self, Z) -> None:
+        if Z is not None:
+            Z = np.asarray(Z)
+            if Z.ndim != 2 or not np.issubdtype(Z.dtype, np.floating):
+                raise ValueError(f"background must be a float [rows, features] array, got "
+                                 f"{Z.dtype} {Z.shape}")
+        self._background = Z
+        if self._device_forest is not None:
+            self._device_forest.set_background(Z)
+
+    def _load_background(self, model_dir: str) -> None:
+        path = os.path.join(model_dir, BACKGROUND_FILE)
+        if os.path.exists(path):
+            self.set_background(np.load(path, allow_pickle=False))
 
     def _set_forest(self, forest: Forest) -> None:
         self._forest = forest
@@ -41,7 +64,10 @@ class GPUForestMixin:
                 if self._device_forest is None:
                     if self._forest is None:
                         raise RuntimeError("model is not loaded")
-                    self._device_forest = DeviceForest(self._forest, self.devices)
+                    dev = DeviceForest(self._forest, self.devices)
+                    if self._background is not None:
+                        dev.set_background(self._background)
+                    self._device_forest = dev
                 dfo = self._device_forest
         return dfo
 
@@ -106,9 +132,20 @@ class GPUForestMixin:
         gets the approximate (Saabas) contributions (TI_OUTPUT_CONTRIB_APPROX),
         shaped as the plain request's; they are served where TreeSHAP is not
         (XGBoost categorical splits, any width and depth).  Both keys together
-        (approximate interactions) are an error."""
+        (approximate interactions) are an error.
+
+        A request with top-level ``"interventional": true`` gets the
+        interventional contributions against the model's background rows
+        (TI_OUTPUT_CONTRIB_INTERV; ``shap.TreeExplainer(model, data)``), shaped
+        as the plain request's, the bias being the background's mean margin.
+        A model without a background, and the key together with either of the
+        other two, is an error."""
         try:
             approx = isinstance(request, dict) and request.get("approx_contribs") is True
+            interv = isinstance(request, dict) and request.get("interventional") is True
+            if interv and (approx or request.get("pred_interactions") is True):
+                raise ValueError('"interventional" together with "pred_interactions" or '
+                                 '"approx_contribs" is not served')
             if approx and request.get("pred_interactions") is True:
                 raise ValueError('"approx_contribs" and "pred_interactions" together '
                                  "(approximate interaction values) are not served")
@@ -120,7 +157,8 @@ class GPUForestMixin:
                 m = m.reshape((m.shape[0], f.n_groups, n, n) if f.n_groups > 1
                               else (m.shape[0], n, n))
                 return {"explanations": m.tolist()}
-            c = self.predict_matrix(X, OUT_CONTRIB_APPROX if approx else OUT_CONTRIB)
+            c = self.predict_matrix(X, OUT_CONTRIB_INTERV if interv
+                                    else OUT_CONTRIB_APPROX if approx else OUT_CONTRIB)
             if f.n_groups > 1:
                 c = c.reshape(c.shape[0], f.n_groups, f.n_features + 1)
             return {"explanations": c.tolist()}

@@ -30,7 +30,7 @@ from typing import Callable, List, Optional, Tuple
 
 import numpy as np
 
-from .forest import (OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_INTERACT, OUT_LEAF, OUT_MARGIN, OUT_PREDICT,
+from .forest import (OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_CONTRIB_INTERV, OUT_INTERACT, OUT_LEAF, OUT_MARGIN, OUT_PREDICT,
                      TI_F32, Forest)
 
 
@@ -94,10 +94,15 @@ class TreeShardedForest:
         """X: [rows, cols] tensor on this rank's device (every rank passes the
         same rows).  Returns the full output on the root (PREDICT and LEAF
         shaped as DeviceForest.predict returns them, MARGIN [rows, K], CONTRIB
-        and CONTRIB_APPROX [rows, K * (F + 1)]) and None elsewhere."""
+        and CONTRIB_APPROX [rows, K * (F + 1)]) and None elsewhere.
+        OUT_INTERACT and OUT_CONTRIB_INTERV are not served tree-sharded: both
+        raise ValueError."""
         if kind == OUT_INTERACT:   # it would fall through to the margin path below
             raise ValueError("kind OUT_INTERACT (SHAP interaction values) is not served "
                              "tree-sharded; use DeviceForest.predict")
+        if kind == OUT_CONTRIB_INTERV:   # no rank's engine holds a background
+            raise ValueError("kind OUT_CONTRIB_INTERV (interventional contributions) is not "
+                             "served tree-sharded; use DeviceForest.predict")
         import torch
         import torch.distributed as dist
         rows, cols = int(X.shape[0]), int(X.shape[1])
