@@ -101,6 +101,7 @@ int upload_device(const ti_forest* f, DeviceForest& d, int device) {
       up(&d.tx8_ord, h.rec.tx8_ord);
     }
     if (stages_trees(L)) up(&d.lx_stage, h.rec.lx_stage);
+    if (L == kLayoutCatRecord) up(&d.cat_limit, h.rec.cat_limit);
     up(&d.leaf_base, h.leaf_base);
     if (f->LW > 1) up(&d.leaves, h.leaves);   // vector leaves are read from the leaf table
     up(&d.exp_leaf_ids, h.exp_leaf_ids);
@@ -403,8 +404,8 @@ int plan_launch(const ti_forest* f, const DeviceForest& d, int xdt, int kind, La
       a.n_stages = f->n_stages;
       p->lds = std::max(static_cast<size_t>(a.stage_off) + static_cast<size_t>(f->lx_stage_cap), kLxMinLds);
       if (p->lds > kLdsPerCu || static_cast<int64_t>(kLxPf) * 16 * R < f->lx_stage_cap)
-        return fail(TI_ERR_UNSUPPORTED, f->layout == kLayoutStaged ? "staged record layout exceeds LDS"
-                                                       : "heap-top staged layout exceeds LDS");
+        return fail(TI_ERR_UNSUPPORTED, f->layout == kLayoutTopStaged ? "heap-top staged layout exceeds LDS"
+                                                          : "staged record layout exceeds LDS");
       a.bin_chunk = bin_chunk_for(static_cast<size_t>(f->lx_stage_cap), R, xdt, f->F);
     } else if (f->layout == kLayoutHeapTop) {   // stages of hx_stage heap tops
       a.tree_stride = static_cast<int64_t>(8) << f->hx_top;   // 2^(D0+1) u32
@@ -423,6 +424,9 @@ int plan_launch(const ti_forest* f, const DeviceForest& d, int xdt, int kind, La
                  : f->tx8 ? ti::Walk::BottomU8 : ti::Walk::HeapTopStaged;
       key.bins16 = rx.b8 == 0;
       if (f->tx8 == 3) p->block = 2 * R;   // two lanes a row
+    } else if (f->layout == kLayoutCatRecord) {   // one rule a forest (plan_crecord)
+      a.cat_limit = d.cat_limit;
+      key.walk = f->has_cat_xgb != 0 ? ti::Walk::CatRecordXgb : ti::Walk::CatRecordLgb;
     } else {
       key.walk = f->layout == kLayoutRecord ? ti::Walk::Record
                  : f->layout == kLayoutStaged ? ti::Walk::StagedRecord : ti::Walk::HeapTopRecord;

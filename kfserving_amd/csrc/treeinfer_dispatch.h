@@ -1,7 +1,8 @@
 // treeinfer_dispatch.h — kernel selection across the translation units.  Each
 // treeinfer_k_<x><a>.hip instantiates every kernel of one (input type,
-// accumulator type) pair and treeinfer_k_cat.hip the categorical heap's for
-// all four pairs, so the five compile in parallel.
+// accumulator type) pair, treeinfer_k_cat.hip the categorical heap's and
+// treeinfer_k_crec.hip the categorical records' for all four pairs, so the six
+// compile in parallel.
 //
 // The host names what it launches with a KernelKey; ti::select(key) is the one
 // way from a key to a kernel.  Each rule that turns a runtime value into a
@@ -33,6 +34,8 @@ enum class Walk {
   BottomU16Split,   // 9: the u16 bottom, two lanes a row t16split_predict_kernel
   CatHeapXgb,       // 10: categorical heap, XGBoost's rule   cheap_predict_kernel
   CatHeapLgb,       // 10: categorical heap, LightGBM's rule  (treeinfer_cheap.h)
+  CatRecordXgb,     // 11: categorical records, XGBoost's rule   crexplicit_predict_kernel
+  CatRecordLgb,     // 11: categorical records, LightGBM's rule  (treeinfer_crec.h)
 };
 
 struct KernelKey {
@@ -132,6 +135,9 @@ KernelFn select_walk(const KernelKey& k) {
     case Walk::CatHeapXgb:
     case Walk::CatHeapLgb:
       break;   // kernels_cat
+    case Walk::CatRecordXgb:
+    case Walk::CatRecordLgb:
+      break;   // kernels_crec
   }
   return nullptr;
 }
@@ -148,9 +154,11 @@ KernelFn kernels_fd(const KernelKey& k);    // float X, double acc
 KernelFn kernels_dd(const KernelKey& k);    // double X, double acc
 KernelFn kernels_df(const KernelKey& k);    // double X, float acc
 KernelFn kernels_cat(const KernelKey& k);   // the categorical heap, every pair
+KernelFn kernels_crec(const KernelKey& k);  // the categorical records, every pair
 
 inline KernelFn select(const KernelKey& k) {
   if (k.walk == Walk::CatHeapXgb || k.walk == Walk::CatHeapLgb) return kernels_cat(k);
+  if (k.walk == Walk::CatRecordXgb || k.walk == Walk::CatRecordLgb) return kernels_crec(k);
   if (!k.x64) return k.acc64 ? kernels_fd(k) : kernels_ff(k);
   return k.acc64 ? kernels_dd(k) : kernels_df(k);
 }

@@ -188,13 +188,19 @@ enum Layout : int32_t {
   kLayoutHeapTop = 8,     //   heap tops in LDS, the rest gathered
   kLayoutTopStaged = 9,   //   heap top + bottom, staged whole trees at a time
   kLayoutCatHeap = 10,    // categorical heap (the heap's fields)
+  kLayoutCatRecord = 11,  // layout 7 for categorical forests: category codes in the bin
+                          //   image, each tree's bitset runs staged behind its records
 };
 // the record family: binned features, rx[] plans, the leaf tables of layout 1
-constexpr bool is_record(int32_t l) { return l >= kLayoutRecord && l <= kLayoutTopStaged; }
+constexpr bool is_record(int32_t l) {
+  return (l >= kLayoutRecord && l <= kLayoutTopStaged) || l == kLayoutCatRecord;
+}
 // a heap top of hx_top levels in LDS
 constexpr bool has_heap_top(int32_t l) { return l == kLayoutHeapTop || l == kLayoutTopStaged; }
 // whole trees staged in LDS: lx_stage / lx_stage_cap / lx_ilp / n_stages
-constexpr bool stages_trees(int32_t l) { return l == kLayoutStaged || l == kLayoutTopStaged; }
+constexpr bool stages_trees(int32_t l) {
+  return l == kLayoutStaged || l == kLayoutTopStaged || l == kLayoutCatRecord;
+}
 // the heap's fields: stride32/64, rows32/64, heap32/64 images
 constexpr bool heap_fields(int32_t l) { return l == kLayoutHeap || l == kLayoutCatHeap; }
 
@@ -257,6 +263,7 @@ struct ForestPtrs {
   void* tx8_val = nullptr;       //   leaf value per bottom position (ACC)
   int32_t* tx8_ord = nullptr;    //   leaf ordinal per bottom position
   uint32_t* hx_top[2] = {nullptr, nullptr};   // heap tops of layouts 8 and 9, per input dtype
+  int32_t* cat_limit = nullptr;  // layout 11: per feature the category code limit, -1 numerical
   // linear leaves (treeinfer_linear.h): leaf records, their terms, first record of each tree
   ti::LinLeaf* lin_leaves = nullptr;
   ti::LinTerm* lin_terms = nullptr;
@@ -491,6 +498,8 @@ struct RecArrays {
   std::vector<uint32_t> tx8_pos;
   std::vector<unsigned char> tx8_val;
   std::vector<int32_t> tx8_ord;
+  // layout 11: per feature L_f = 32 x its longest bitset in words, -1 for a numerical feature
+  std::vector<int32_t> cat_limit;
 };
 
 // Every packed array that exists only to be uploaded.  The forest owns one

@@ -127,6 +127,9 @@ struct KArgs {
   // shared
   const int32_t* tree_group;      // [T]
   void* out;
+  // categorical records (11), last so that every other field keeps its offset:
+  // per feature the code limit L_f, -1 for a numerical feature
+  const int32_t* cat_limit;       // [F]
 };
 
 __device__ __forceinline__ size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
@@ -1579,6 +1582,24 @@ __global__ void __launch_bounds__(512) explicit_predict_kernel(const KArgs a) {
 constexpr uint32_t kRxNanLeft = 1u;
 constexpr uint32_t kRxZeroFlip = 4u;
 constexpr uint32_t kRxOffMask = 0xFFFAu;   // the bin byte offset without the flag bits
+// Categorical records (layout 11, treeinfer_crec.h): a categorical node's x
+// carries kCrCat (bit 3, in the lane part like the zero flip) and in its high
+// half the byte offset of its bitset run in the tree's block, not a rank.
+constexpr uint32_t kCrCat = 8u;
+constexpr uint32_t kCrOffMask = 0xFFF2u;   // kRxOffMask without kCrCat
+// The bin of a categorical column: the category code both rules read, with
+// every value that "goes where non-members go" folded into the limit `lim`
+// (= 32 x the longest bitset on the feature, in words; the runs end in a zero
+// word there).  CAT 1, LightGBM: trunc(x) for -1 < x < 2^31, else (NaN too)
+// lim.  CAT 2, XGBoost: NaN keeps the image's NaN code (the node's default
+// child); trunc(x) for 0 <= x < 2^24 (-0.0 is category 0), else lim.
+template <int CAT, typename XT>
+__device__ __forceinline__ uint32_t cat_bin(XT x, uint32_t lim, uint32_t nan_code) {
+  if (CAT == 2 && x != x) return nan_code;
+  const bool ok = CAT == 2 ? (x >= XT(0) && x < XT(16777216.0)) : (x > XT(-1) && x < XT(2147483648.0));
+  const uint32_t v = ok ? (uint32_t)(int32_t)(ok ? x : XT(0)) : lim;
+  return v < lim ? v : lim;
+}
 // u8 bins (layout 9 when every feature has <= 254 distinct thresholds, <= 126
 // with the zero rule; lightgbm max_bin = 255 models): four features per word,
 // so the byte offset keeps bits 0-1 and the flags move into the lane part
@@ -1672,7 +1693,10 @@ __device__ __forceinline__ uint16_t lds_rxbin(uint32_t byte_addr) {
 // Search Q consecutive features [f0, f0 + Q) of the lane's row (values x,
 // NaN past the last feature) and store their packed u16 bins in the image
 // (f0 even).  With ZB (zero-missing forests) b2 = 2 b + (x == 0), NaN 0xFFFE.
-template <typename XT, bool ZB, bool KARY, int Q, bool SROOT = false, bool B8 = false>
+// CAT (layout 11: 1 LightGBM's rule, 2 XGBoost's): a feature with a.cat_limit
+// >= 0 is categorical and stores cat_bin of its value instead of a rank; its
+// exact zeros do not ask for the slow step.
+template <typename XT, bool ZB, bool KARY, int Q, bool SROOT = false, bool B8 = false, int CAT = 0>
 __device__ __forceinline__ void rx_bin_group(const KArgs& a, const XT (&x)[Q], int f0, int R, int tid,
                                              bool& has_nan) {
   const int F = a.n_features;
@@ -1739,12 +1763,16 @@ __device__ __forceinline__ void rx_bin_group(const KArgs& a, const XT (&x)[Q], i
   for (int j = 0; j < Q / P; ++j) w[j] = 0u;
 #pragma unroll
   for (int q = 0; q < Q; ++q) {
+    int32_t lim = -1;   // >= 0: a categorical feature's code limit
+    if constexpr (CAT != 0) lim = a.cat_limit[f0 + q < F ? f0 + q : F - 1];
     const bool nan = x[q] != x[q];
-    const bool zero = ZB && x[q] == XT(0);
+    const bool zero = ZB && x[q] == XT(0) && (CAT == 0 || lim < 0);
     has_nan |= (nan || zero) && (f0 + q < F);   // the tile needs the slow step
     uint32_t b = 1u + k[q] - tsz;
     if (ZB) b = nan ? kNan : 2u * b + (zero ? 1u : 0u);
     else b = nan ? kNan : b;
+    if constexpr (CAT != 0)
+      if (lim >= 0) b = cat_bin<CAT>(x[q], (uint32_t)lim, kNan);
     w[q / P] |= b << ((q % P) * (32 / P));
   }
 #pragma unroll
@@ -1770,7 +1798,7 @@ __device__ __forceinline__ void rx_bin_group(const KArgs& a, const XT (&x)[Q], i
 // exact 0.
 // NT threads bin the R-row tile (NT = R, or 2R for the two-lanes-a-row walk:
 // thread tid takes row tid mod R and every (NT / R)-th group of Q features).
-template <typename XT, bool ZB, bool KARY = false, bool SROOT = false, bool B8 = false>
+template <typename XT, bool ZB, bool KARY = false, bool SROOT = false, bool B8 = false, int CAT = 0>
 __device__ __forceinline__ bool rx_stage_bins_impl(volatile int* flag, XT* temp, const KArgs& a,
                                                    int64_t row0, int R, int tid_in, int NT) {
   constexpr int Q = TI_RX_BINQ;
@@ -1806,7 +1834,7 @@ __device__ __forceinline__ bool rx_stage_bins_impl(volatile int* flag, XT* temp,
         XT x[Q];
 #pragma unroll
         for (int q = 0; q < Q; ++q) x[q] = c + q < kc ? temp[(c + q) * R + tid] : nan_value<XT>();
-        rx_bin_group<XT, ZB, KARY, Q, SROOT, B8>(a, x, f0 + c, R, tid, has_nan);
+        rx_bin_group<XT, ZB, KARY, Q, SROOT, B8, CAT>(a, x, f0 + c, R, tid, has_nan);
       }
     }
   } else {
@@ -1818,7 +1846,7 @@ __device__ __forceinline__ bool rx_stage_bins_impl(volatile int* flag, XT* temp,
         const int f = f0 + q < F ? f0 + q : F - 1;
         x[q] = f0 + q < FC ? zero_map(xr[f], a.lgb_zero_map) : nan_value<XT>();
       }
-      rx_bin_group<XT, ZB, KARY, Q, SROOT, B8>(a, x, f0, R, tid, has_nan);
+      rx_bin_group<XT, ZB, KARY, Q, SROOT, B8, CAT>(a, x, f0, R, tid, has_nan);
     }
   }
   __syncthreads();   // flag = 0 is visible before any lane sets it
@@ -1831,15 +1859,15 @@ __device__ __forceinline__ bool rx_stage_bins_impl(volatile int* flag, XT* temp,
 // 0: float32 16-byte nodes, float64 32-byte ones), else the Eytzinger tables.
 // SROOT: the 5-ary root as a scalar load (layout 8: C4 2.17 -> 2.13 ms; on
 // layout 9 it cost C3 0.7 %, profiles/r2_kary_root_sweep.jsonl)
-template <typename XT, bool ZB, bool SROOT = false, bool B8 = false>
+template <typename XT, bool ZB, bool SROOT = false, bool B8 = false, int CAT = 0>
 __device__ __forceinline__ bool rx_stage_bins(volatile int* flag, const KArgs& a, int64_t row0,
                                               int R, int tid, void* temp = nullptr, int NT = 0) {
   if (NT <= 0) NT = R;
   if (a.bin_kary > 0)
-    return rx_stage_bins_impl<XT, ZB, true, SROOT, B8>(flag, static_cast<XT*>(temp), a, row0, R,
-                                                       tid, NT);
-  return rx_stage_bins_impl<XT, ZB, false, false, B8>(flag, static_cast<XT*>(temp), a, row0, R, tid,
-                                                      NT);
+    return rx_stage_bins_impl<XT, ZB, true, SROOT, B8, CAT>(flag, static_cast<XT*>(temp), a, row0,
+                                                            R, tid, NT);
+  return rx_stage_bins_impl<XT, ZB, false, false, B8, CAT>(flag, static_cast<XT*>(temp), a, row0, R,
+                                                           tid, NT);
 }
 
 // Per step every tree's bin read is issued first, then each tree's decision

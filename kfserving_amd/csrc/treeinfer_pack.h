@@ -806,9 +806,20 @@ bool plan_rx_slots(const ti_forest_desc* d, RecSlots* out) {
 // u8 images hold four bins a word, so a tile of twice the rows (512,
 // TI_RX_ROWS8) fits the LDS a u16 tile of 256 takes: 4 waves per SIMD
 // instead of 2 at C3's 100 features.
+//
+// With `cp` (layout 11, plan_crec_blocks) tree t's records start at slot
+// cp->base[t] of an image that also holds the bitset runs, and a categorical
+// node gets the categorical record of treeinfer_crec.h and its run: the
+// node's bitset, the zero words up to the feature's W_f + 1 left as assigned.
+struct CatRecPlan {
+  std::vector<int32_t> limit;      // [F] L_f = 32 W_f of a categorical feature, -1 numerical
+  std::vector<uint32_t> base;      // [T+1] first slot of each tree's block
+  std::vector<uint32_t> run_off;   // per node: byte offset of a categorical node's run in its block
+};
 template <typename XT, typename ACC>
 bool pack_rexplicit(const ti_forest_desc* d, const ti_forest* f,
-                    const std::vector<uint32_t>& slot_of, RecExplicit* out, bool b8) {
+                    const std::vector<uint32_t>& slot_of, RecExplicit* out, bool b8,
+                    const CatRecPlan* cp = nullptr) {
   const bool zero = f->zero_rule != 0;
   const RankTables<XT> rt = collect_ranks<XT>(d, zero);
   if (rt.m_max > (b8 ? (zero ? 126u : 254u) : (zero ? 16382u : 65533u))) return false;
@@ -833,10 +844,12 @@ bool pack_rexplicit(const ti_forest_desc* d, const ti_forest* f,
   if (env_int(sizeof(XT) == 4 ? "TI_KARY" : "TI_KARY64", 1) != 0) kary_tables(rt, &rx->tbl, &rx->kary);
   else eytzinger_tables(rt, &rx->tbl);
   // an even slot count: the staged layout copies whole 16-byte words
-  rx->recs.assign(d->n_nodes + (d->n_nodes & 1), uint2{0u, 0u});
+  const int64_t n_slots = cp ? cp->base[d->n_trees] : d->n_nodes;
+  rx->recs.assign(n_slots + (n_slots & 1), uint2{0u, 0u});
   const bool scalar_leaves = d->leaf_width == 1;
   for (int t = 0; t < d->n_trees; ++t) {
     const int64_t b = d->tree_offset[t];
+    const int64_t rb = cp ? cp->base[t] : b;   // the tree's first slot in the image
     for (int64_t g = b; g < d->tree_offset[t + 1]; ++g) {
       uint2 r{0u, 0u};
       if (d->feature[g] < 0) {
@@ -844,6 +857,14 @@ bool pack_rexplicit(const ti_forest_desc* d, const ti_forest* f,
           const ACC v = static_cast<ACC>(d->leaf_value[g]);
           std::memcpy(&r, &v, sizeof(ACC));
         }
+      } else if (cp && (d->flags[g] & TI_NODE_CATEGORICAL)) {
+        const int fe = d->feature[g];
+        const uint32_t off = static_cast<uint32_t>((fe / P) * R * 4 + (fe % P) * (4 / P));
+        r.x = off | ti::kCrCat | ((d->flags[g] & TI_NODE_NAN_LEFT) ? nan_left : 0u) |
+              (cp->run_off[g] << 16);
+        r.y = (slot_of[b + d->right[g]] << 16) | slot_of[b + d->left[g]];
+        uint32_t* run = reinterpret_cast<uint32_t*>(&rx->recs[rb]) + cp->run_off[g] / 4;
+        std::copy(d->cat_bits + d->cat_offset[g], d->cat_bits + d->cat_offset[g] + d->cat_nwords[g], run);
       } else {
         const int fe = d->feature[g];
         const uint32_t off = static_cast<uint32_t>((fe / P) * R * 4 + (fe % P) * (4 / P));
@@ -857,7 +878,7 @@ bool pack_rexplicit(const ti_forest_desc* d, const ti_forest* f,
         }
         r.y = (slot_of[b + d->right[g]] << 16) | slot_of[b + d->left[g]];
       }
-      rx->recs[b + slot_of[g]] = r;
+      rx->recs[rb + slot_of[g]] = r;
     }
   }
   *out = std::move(view);
@@ -887,7 +908,12 @@ size_t lx_stage_area(const RecArrays& c, int R) {
   cap = cap > bins ? cap - bins : 0;
   return std::min(cap, static_cast<size_t>(kLxPf) * 16 * R) & ~size_t(15);
 }
-bool plan_lx_stages(const RecSlots& s, RecCandidate* c, int T) {
+// whole_groups (layout 11): lx_ilp is chosen from the uncut stages as for
+// layout 7, then a stage that holds more than lx_ilp trees and is not the last
+// is cut to a whole number of groups of lx_ilp trees, as plan_tx cuts its
+// stages.  A stage of fewer than lx_ilp trees, and the last one, still walk
+// duplicate trees in their short group (rx_leaves skips them).
+bool plan_lx_stages(const RecSlots& s, RecCandidate* c, int T, bool whole_groups = false) {
   const int R = c->rx[0].rows;
   if (c->rx[1].rows != R) return false;
   const size_t cap = lx_stage_area(*c, R);
@@ -898,14 +924,18 @@ bool plan_lx_stages(const RecSlots& s, RecCandidate* c, int T) {
   size_t biggest = 0;
   for (int t = 0; t < T; ++t) biggest = std::max(biggest, span(t, t + 1));
   if (T < 2 || cap < 2 * biggest + 16) return false;
-  c->lx_stage.assign(1, 0);
-  int t0 = 0;
-  while (t0 < T) {
-    int t1 = t0 + 1;
-    while (t1 < T && span(t0, t1 + 1) <= cap) ++t1;
-    c->lx_stage.push_back(t1);
-    t0 = t1;
-  }
+  auto cut_stages = [&](int cut) {
+    c->lx_stage.assign(1, 0);
+    int t0 = 0;
+    while (t0 < T) {
+      int t1 = t0 + 1;
+      while (t1 < T && span(t0, t1 + 1) <= cap) ++t1;
+      if (cut && t1 < T && t1 - t0 > cut) t1 = t0 + ((t1 - t0) / cut) * cut;
+      c->lx_stage.push_back(t1);
+      t0 = t1;
+    }
+  };
+  cut_stages(0);
   c->lx_stage_cap = static_cast<int64_t>(cap);
   // children as byte offsets in the tree (a stage is <= 32 KB: < 8,192 slots)
   for (auto& rx : c->rx)
@@ -921,6 +951,69 @@ bool plan_lx_stages(const RecSlots& s, RecCandidate* c, int T) {
   c->lx_ilp = per_stage >= 7.5 ? 8 : per_stage >= 6.5 ? 7 : 4;
   const int force_ilp = env_int("TI_LX_ILP", 0);
   if (force_ilp > 0) c->lx_ilp = force_ilp >= 8 ? 8 : force_ilp == 7 ? 7 : 4;
+  if (whole_groups) cut_stages(c->lx_ilp);
+  return true;
+}
+
+// Layout 11 (treeinfer_crec.h): layout 7 for a forest with categorical splits.
+// It takes a forest whose categorical nodes use one rule (XGBoost's only
+// without the LightGBM zero rule: the kernel pairs that with LightGBM's), in
+// which no feature is split both numerically and categorically (the image
+// holds one u16 a feature), whose longest bitset W_f on each categorical
+// feature is at most kCrMaxWords words (every code of the run's W_f + 1 words,
+// L_f = 32 W_f included, stays below the image's NaN codes), and whose blocks
+// -- a tree's records, then its categorical nodes' runs of W_f + 1 words,
+// padded to whole slots -- fit the stages of plan_lx_stages two at a time.
+constexpr int kCrMaxWords = 2046;
+bool plan_crec_blocks(const ti_forest_desc* d, const ti_forest* f, RecSlots* s, CatRecPlan* cp) {
+  if (!f->has_cat || (f->has_cat_xgb && (f->has_cat_lgb || f->zero_rule))) return false;
+  const int F = d->n_features, T = d->n_trees;
+  std::vector<int32_t> words(F, -1);   // W_f; -1: no categorical node tests f
+  std::vector<char> numerical(F, 0);
+  for (int64_t g = 0; g < d->n_nodes; ++g) {
+    if (d->feature[g] < 0) continue;
+    if (d->flags[g] & TI_NODE_CATEGORICAL) words[d->feature[g]] = std::max(words[d->feature[g]], d->cat_nwords[g]);
+    else numerical[d->feature[g]] = 1;
+  }
+  cp->limit.assign(F, -1);
+  for (int fe = 0; fe < F; ++fe) {
+    if (words[fe] < 0) continue;
+    if (numerical[fe] || words[fe] > kCrMaxWords) return false;
+    cp->limit[fe] = 32 * words[fe];
+  }
+  if (!plan_rx_slots(d, s)) return false;
+  cp->base.assign(T + 1, 0);
+  cp->run_off.assign(d->n_nodes, 0);
+  uint64_t at = 0;   // slots so far
+  for (int t = 0; t < T; ++t) {
+    cp->base[t] = static_cast<uint32_t>(at);
+    uint64_t n = static_cast<uint64_t>(d->tree_offset[t + 1] - d->tree_offset[t]);
+    for (int64_t g = d->tree_offset[t]; g < d->tree_offset[t + 1]; ++g) {
+      if (d->feature[g] < 0 || !(d->flags[g] & TI_NODE_CATEGORICAL)) continue;
+      cp->run_off[g] = static_cast<uint32_t>(n * 8);
+      n += (static_cast<uint64_t>(words[d->feature[g]]) + 2) / 2;   // W_f + 1 words in whole slots
+    }
+    if (n * 8 > 65528) return false;   // run and child byte offsets are 16 bits
+    at += n;
+    if (at >= (uint64_t(1) << 28)) return false;   // byte offsets of the image stay 32 bits
+  }
+  cp->base[T] = static_cast<uint32_t>(at);
+  s->rx_base = cp->base;
+  s->rx_slots = static_cast<int64_t>(at);
+  return true;
+}
+
+bool plan_crecord(const ti_forest_desc* d, const ti_forest* f, RecSlots* s, RecCandidate* out) {
+  CatRecPlan cp;
+  if (!plan_crec_blocks(d, f, s, &cp)) return false;
+  RecCandidate c;
+  if (!for_views(f->accum, [&](auto x, auto acc, int i) {
+        return pack_rexplicit<decltype(x), decltype(acc)>(d, f, s->slot_of, &c.rx[i], false, &cp);
+      }))
+    return false;
+  if (!plan_lx_stages(*s, &c, f->T, true)) return false;
+  c.cat_limit = std::move(cp.limit);
+  *out = std::move(c);
   return true;
 }
 
@@ -1492,9 +1585,12 @@ void commit_records(ti_forest* f, RecSlots&& s, RecCandidate&& c) {
 // categorical splits: the categorical heap (10) for XGBoost-rule forests of
 // depth <= 8 whose records fit a stage (plan_cheap), the float explicit kernel
 // (1) otherwise and for every LightGBM-rule forest;
-// TI_FORCE_LAYOUT=heap|explicit|rexplicit|lexplicit|hexplicit|texplicit|cheap
+// LightGBM-rule forests deeper than 8 take the categorical records (11) where
+// plan_crecord accepts them;
+// TI_FORCE_LAYOUT=heap|explicit|rexplicit|lexplicit|hexplicit|texplicit|cheap|crecord
 // overrides (tests run every layout on the same forest); cheap puts any
-// categorical forest of depth <= 8 on layout 10, whichever rule it uses.
+// categorical forest of depth <= 8 on layout 10, whichever rule it uses, and
+// crecord any categorical forest that plan_crecord accepts on layout 11.
 int choose_layout(const ti_forest_desc* desc, ti_forest* f) {
   HostImage& h = *f->host;
   const size_t acc_sz = f->accum == TI_F64 ? 8 : 4;
@@ -1569,8 +1665,19 @@ int choose_layout(const ti_forest_desc* desc, ti_forest* f) {
     // record explicit slots (layout 6) unless a categorical split needs raw
     // values or another explicit kernel is forced
     RecSlots slots;
-    bool rx_ok = !f->has_cat && want != "explicit" && plan_rx_slots(desc, &slots);
     RecCandidate c;
+    // a categorical forest takes its category codes (layout 11) when forced, or
+    // when it is a LightGBM-rule forest too deep for the heaps, and is then
+    // done: slots and c are committed (moved from), and the record family
+    // below must not plan with them again, whatever rx_ok comes to mean
+    const bool crec = f->has_cat &&
+                      (want == "crecord" || (want.empty() && !f->has_cat_xgb && D > kMaxHeapDepth)) &&
+                      plan_crecord(desc, f, &slots, &c);
+    if (crec) {
+      chosen = kLayoutCatRecord;
+      commit_records(f, std::move(slots), std::move(c));
+    }
+    bool rx_ok = !crec && !f->has_cat && want != "explicit" && plan_rx_slots(desc, &slots);
     auto pack_views = [&](bool b8) {
       c = RecCandidate();
       return for_views(f->accum, [&](auto x, auto acc, int i) {
