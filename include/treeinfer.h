@@ -104,6 +104,20 @@
  *   n_cols == n_features at predict (TI_ERR_INVALID otherwise); S > 16, and
  *   pre-steps together with linear leaves, are TI_ERR_UNSUPPORTED; an unknown
  *   op code, or S > 0 with a null pre_op or pre_const, is TI_ERR_INVALID.
+ *
+ * Weighted quantiles across trees (ABI 11; TI_OUTPUT_TREE_QUANTILE, sklearn's
+ * AdaBoostRegressor.predict): for a row let v[t] be the leaf value of the leaf
+ * it reaches in tree t (the walk above, pre-steps included; no divisor, no base
+ * margin) and w[t] = desc.tree_weight[t] (NULL: every weight 1.0).
+ *   1. order the trees by (v[t], t) ascending: ties (-0.0 equals +0.0) go to the
+ *      lower tree index, a NaN value sorts last;
+ *   2. cdf[p] = fl(cdf[p-1] + w[order[p]]) in float64, one add a position in
+ *      that order, cdf[-1] = 0 (numpy's cumsum; a pairwise or scanned sum is
+ *      another rule: it can move step 3's position);
+ *   3. level q answers v[order[p]] at the first p with cdf[p] >= fl(q * cdf[T-1])
+ *      (p = 0 when no position qualifies, as numpy's argmax of the mask gives).
+ *   The levels are ti_forest_set_quantiles', {0.5} by default: the weighted
+ *   median.  The answer is an element of v, bit for bit.
  */
 #ifndef TREEINFER_H_
 #define TREEINFER_H_
@@ -114,7 +128,7 @@
 extern "C" {
 #endif
 
-#define TI_ABI_VERSION 10
+#define TI_ABI_VERSION 11
 
 /* return codes */
 #define TI_OK               0
@@ -228,6 +242,18 @@ extern "C" {
                               /* through the pre-pass for this kind), with K *   */
                               /* (F + 1) > 128 or with a root-to-leaf path of    */
                               /* more than 32 distinct features.                 */
+#define TI_OUTPUT_TREE_QUANTILE 7
+                              /* ABI 11: weighted quantiles of a row's per-tree  */
+                              /* predictions (the rule above), [rows, n_q] in    */
+                              /* the accumulator type, n_q the levels of         */
+                              /* ti_forest_set_quantiles.  Two calls give the    */
+                              /* same bits.  TI_ERR_UNSUPPORTED for leaf_width   */
+                              /* != 1 or n_groups != 1, for linear leaves, for a */
+                              /* tree whose leaf ids are negative or not         */
+                              /* distinct, and for more than 4,096 trees.  The   */
+                              /* host pipeline sizes its row chunks by the wider */
+                              /* of the input row and the 4 * T bytes of leaf    */
+                              /* ids a row takes between the two passes.         */
 
 /*
  * Canonical forest: host structure-of-arrays over the nodes of all trees,
@@ -291,6 +317,11 @@ typedef struct ti_forest_desc {
   int32_t reserved1;
   const int32_t* pre_op;      /* [S]     TI_PRE_* of each step                      */
   const double*  pre_const;   /* [S * F] constant of step s for column f            */
+  /* tree weights (ABI 11); NULL: every weight is 1.0.  Read by
+   * TI_OUTPUT_TREE_QUANTILE alone (AdaBoostRegressor.estimator_weights_); no
+   * other output kind changes with them.  Each must be >= 0 and not NaN
+   * (TI_ERR_INVALID); zero is legal. */
+  const double*  tree_weight; /* [T]                                                */
 } ti_forest_desc;
 
 typedef struct ti_forest ti_forest;   /* opaque, owns device memory */
@@ -384,6 +415,16 @@ int ti_forest_get_info(const ti_forest* forest, ti_forest_info* info);
  * Replaces the `data` argument of shap.TreeExplainer(model, data). */
 int ti_forest_set_background(ti_forest* forest, const void* Z, int32_t z_dtype,
                              int64_t n_rows, int32_t n_cols, int64_t row_stride);
+
+/* ABI 11: the levels of TI_OUTPUT_TREE_QUANTILE, n_q of them, 1 <= n_q <= 8,
+ * each in [0, 1] (TI_ERR_INVALID otherwise; the forest keeps its levels then).
+ * The default is {0.5}.  ti_output_shape reports n_rows * n_q for the kind.
+ * It must be called with no TI_OUTPUT_TREE_QUANTILE call (and no
+ * ti_output_shape for that kind) in flight on the forest; calls of every other
+ * kind read no level and may run beside it.  Replaces nothing in sklearn, whose
+ * AdaBoostRegressor.predict has the median alone; q of a RandomForestRegressor's
+ * per-tree predictions is np.quantile(..., method="inverted_cdf") over them. */
+int ti_forest_set_quantiles(ti_forest* forest, const double* q, int32_t n_q);
 
 /* Per-forest tuning that changes speed, never results (both TreeSHAP kernels
  * produce the same contributions).  0 or TI_ERR_INVALID for an unknown option

@@ -22,6 +22,7 @@
 #include "treeinfer_shap.h"
 #include "treeinfer_shap_interv.h"
 #include "treeinfer_approx.h"
+#include "treeinfer_quantile.h"
 #include "treeinfer_pre.h"
 
 namespace {
@@ -50,6 +51,7 @@ void free_device(DeviceForest& d) {
   free_shap(d);
   free_interv(d);
   free_approx(d);
+  free_quantile(d);
   free_scratch(d);
   if (d.interact_done) (void)hipEventDestroy(d.interact_done);
   if (d.interact_buf) (void)hipFree(d.interact_buf);
@@ -194,6 +196,7 @@ int64_t output_width(const ti_forest* f, int kind) {
   if (kind == TI_OUTPUT_CONTRIB || kind == TI_OUTPUT_CONTRIB_APPROX || kind == TI_OUTPUT_CONTRIB_INTERV)
     return static_cast<int64_t>(f->K) * (f->F + 1);
   if (kind == TI_OUTPUT_INTERACT) return static_cast<int64_t>(f->K) * (f->F + 1) * (f->F + 1);
+  if (kind == TI_OUTPUT_TREE_QUANTILE) return static_cast<int64_t>(f->quant_q.size());
   if (kind == TI_OUTPUT_PREDICT && f->transform == TI_TRANSFORM_ARGMAX) return 1;
   return f->K;
 }
@@ -491,6 +494,8 @@ int launch_any(ti_forest* f, int slot, const void* X, int xdt, int64_t rows, int
                int64_t stride, int kind, void* out, hipStream_t stream);
 int launch_approx(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows, int32_t cols,
                   int64_t stride, void* out, int64_t out_ld, hipStream_t stream);
+int launch_quantile(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows, int32_t cols,
+                    int64_t stride, void* out, hipStream_t stream);
 
 // Host copies into / out of pinned staging: large copies split over threads
 // (one thread moves ~10 GB/s from pageable memory; PCIe Gen5 x16 takes ~55).
@@ -530,10 +535,16 @@ int64_t chunk_rows(size_t row_bytes) {
 // TI_CHUNK_MB bounds the wider of the two rows, in whole 64-row waves (the
 // interaction kernels have no 512-row tile).  Approximate contributions do the
 // same with their K * (F + 1) outputs (their pass 2 has 64-row tiles too).
+// Quantiles across trees write a few elements a row, but a row holds 4 * T
+// bytes of leaf ids between the two passes: that scratch row takes the output
+// row's place.
 int64_t chunk_rows_for(const ti_forest* f, int xdt, int64_t stride, int kind) {
   const size_t x_row = static_cast<size_t>(stride) * dtype_size(xdt);
-  if (kind != TI_OUTPUT_INTERACT && kind != TI_OUTPUT_CONTRIB_APPROX) return chunk_rows(x_row);
-  const size_t o_row = dtype_size(output_dtype(f, kind)) * static_cast<size_t>(output_width(f, kind));
+  if (kind != TI_OUTPUT_INTERACT && kind != TI_OUTPUT_CONTRIB_APPROX && kind != TI_OUTPUT_TREE_QUANTILE)
+    return chunk_rows(x_row);
+  const size_t o_row = kind == TI_OUTPUT_TREE_QUANTILE
+                           ? static_cast<size_t>(4) * f->T
+                           : dtype_size(output_dtype(f, kind)) * static_cast<size_t>(output_width(f, kind));
   const int mb = env_int("TI_CHUNK_MB", 64);
   const int64_t r = static_cast<int64_t>((static_cast<size_t>(std::max(mb, 1)) << 20) /
                                          std::max<size_t>(std::max(x_row, o_row), 1));
@@ -1058,12 +1069,84 @@ int launch_approx(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t
   return rc;
 }
 
+// Quantiles across trees (treeinfer_quantile.h): two stream-ordered passes per
+// row block, as launch_approx has.  Pass 1 is the forest's own walk with
+// TI_OUTPUT_LEAF into a [rows_block, T] int32 scratch of at most 1 GiB; pass 2
+// orders each row's T values and scans their weights: the register kernel for
+// networks of up to 512 keys, the LDS kernel above.
+int launch_quantile(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows, int32_t cols,
+                    int64_t stride, void* out, hipStream_t stream) {
+  if (!f->quant_refused.empty()) return fail(TI_ERR_UNSUPPORTED, f->quant_refused);
+  if (rows <= 0) return TI_OK;
+  int rc = ensure_quantile(f);
+  if (rc) return rc;
+  const int T = f->T;
+  int N = 64;
+  while (N < T) N <<= 1;
+  using QuantFn = void (*)(ti::QuantileArgs);
+  QuantFn fn = ti::tree_quantile_lds_kernel;
+  int block = 0, tile = 0;
+  size_t lds = 0;
+  if (N <= ti::kQRegMaxN) {
+    fn = N == 64 ? ti::tree_quantile_reg_kernel<1> : N == 128 ? ti::tree_quantile_reg_kernel<2>
+         : N == 256 ? ti::tree_quantile_reg_kernel<4> : ti::tree_quantile_reg_kernel<8>;
+    block = ti::kQWaves * 64;
+    tile = ti::kQRegRows;
+    lds = align16(static_cast<size_t>(T) * 8) + static_cast<size_t>(ti::kQRegRows) * (N + 2) * 2;
+  } else {
+    const int waves = static_cast<int>(ti::kQLdsKeyBytes / (static_cast<uint32_t>(N) * 12));
+    block = waves * 64;
+    tile = waves * ti::kQLdsRowsPerWave;
+    lds = ti::kQLdsKeyBytes;
+  }
+  rc = ensure_lds_attr(d.device, reinterpret_cast<KernelFn>(fn));
+  if (rc) return rc;
+  occ_note(reinterpret_cast<KernelFn>(fn), block, lds);
+  const size_t xs = dtype_size(xdt), as = dtype_size(f->accum);
+  const int64_t row_bytes = static_cast<int64_t>(4) * T;
+  int64_t rows_block = (int64_t(1) << 30) / row_bytes;
+  rows_block = std::max<int64_t>(tile, rows_block / tile * tile);
+  ScratchHold ids_buf(d, stream);   // given back behind the last pass 2
+  if (!ids_buf.take(static_cast<size_t>(std::min(rows, rows_block) * row_bytes)))
+    return fail(TI_ERR_NOMEM, "leaf-id scratch allocation failed");
+  int32_t* ids = static_cast<int32_t*>(ids_buf.p);
+  const int n_q = static_cast<int>(f->quant_q.size());
+  for (int64_t r0 = 0; r0 < rows && rc == TI_OK; r0 += rows_block) {
+    const int64_t nb = std::min(rows_block, rows - r0);
+    const void* xb = static_cast<const unsigned char*>(X) + static_cast<size_t>(r0 * stride) * xs;
+    rc = launch(f, d, xb, xdt, nb, cols, stride, TI_OUTPUT_LEAF, ids, stream);
+    if (rc) break;
+    ti::QuantileArgs a;
+    a.leaf_ids = ids;
+    a.leaf_base = d.quant_leaf_base;
+    a.values = d.quant_values;
+    a.weights = d.quant_weights;
+    for (int q = 0; q < ti::kQuantileMaxLevels; ++q) a.q[q] = q < n_q ? f->quant_q[q] : 0.0;
+    a.n_q = n_q;
+    a.n_trees = T;
+    a.n_rows = nb;
+    a.out = static_cast<unsigned char*>(out) + static_cast<size_t>(r0 * n_q) * as;
+    a.out_f32 = f->accum == TI_F32 ? 1 : 0;
+    a.n_pad = N;
+    const int64_t grid = (nb + tile - 1) / tile;
+    if (grid > 0x7fffffff) rc = fail(TI_ERR_INVALID, "too many rows for one launch");
+    if (rc) break;
+    hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(grid)), dim3(block), lds, stream, a);
+    if (hipGetLastError() != hipSuccess) rc = fail(TI_ERR_DEVICE, "tree quantile launch failed");
+  }
+  return rc;
+}
+
 // The forest's walk of X as it stands: every kind, every forest shape.
 int launch_walk(ti_forest* f, int slot, const void* X, int xdt, int64_t rows, int32_t cols,
                 int64_t stride, int kind, void* out, hipStream_t stream) {
   if (kind == TI_OUTPUT_CONTRIB_APPROX && f->parts.empty())
     return launch_approx(f, *f->devs[slot], X, xdt, rows, cols, stride, out, output_width(f, kind),
                          stream);
+  if (kind == TI_OUTPUT_TREE_QUANTILE) {   // a forest in group parts has n_groups > 1: refused
+    if (!f->parts.empty()) return fail(TI_ERR_UNSUPPORTED, f->quant_refused);
+    return launch_quantile(f, *f->devs[slot], X, xdt, rows, cols, stride, out, stream);
+  }
   if (kind == TI_OUTPUT_CONTRIB && f->linear)
     return fail(TI_ERR_UNSUPPORTED,
                 "TI_OUTPUT_CONTRIB of a forest with linear leaves (LightGBM itself refuses "
@@ -1155,6 +1238,7 @@ int create_chunked(const ti_forest_desc* d, const std::vector<int>& depth, const
   std::unique_ptr<ti_forest> f(new ti_forest());
   fill_model(d, depth, f.get());
   f->lgb_zero_map = 0;   // the parts hold it: a parent launches no tree kernel
+  keep_quantile_source(d, f.get());   // more than 16 groups: the refusal alone
   const int K = d->n_groups, LW = d->leaf_width;
   for (int k0 = 0; k0 < K; k0 += ti::kMaxGroups) {
     const int kc = std::min(ti::kMaxGroups, K - k0);
@@ -1209,6 +1293,7 @@ int create_chunked(const ti_forest_desc* d, const std::vector<int>& depth, const
     sd.cat_offset = d->cat_offset ? cat_off.data() : nullptr;
     sd.cat_nwords = d->cat_offset ? cat_nw.data() : nullptr;
     sd.cover = d->cover ? cov.data() : nullptr;
+    sd.tree_weight = nullptr;   // read by the quantile kind alone, which the parent refuses
     if (k0 > 0) {   // the first part's replicas hold the pre-step arrays
       sd.n_pre_steps = 0;
       sd.pre_op = nullptr;
@@ -1221,6 +1306,8 @@ int create_chunked(const ti_forest_desc* d, const std::vector<int>& depth, const
       return rc;
     }
     part->pre_steps = 0;   // the parent transforms X once (launch_any); no part does
+    part->quant_tab.reset();   // nor is a part asked for quantiles: the parent refuses them
+    part->quant_refused = f->quant_refused;
     f->parts.emplace_back(part);
     f->part_k0.push_back(k0);
     f->part_trees.push_back(std::move(trees));
@@ -1274,6 +1361,7 @@ int ti_forest_create(const ti_forest_desc* desc, const int32_t* devices, int32_t
   if (desc->lin_offset && (rc = pack_linear(desc, f->host.get()))) return rc;
   keep_shap_source(desc, f.get());
   keep_approx_source(desc, f.get());
+  keep_quantile_source(desc, f.get());
   if (desc->n_pre_steps > 0) {
     f->host->pre_op.assign(desc->pre_op, desc->pre_op + desc->n_pre_steps);
     f->host->pre_const.assign(desc->pre_const,
@@ -1338,6 +1426,17 @@ int ti_forest_set_background(ti_forest* f, const void* Z, int32_t zdt, int64_t B
     for (int k = 0; k < K; ++k) bias[k] /= static_cast<double>(B);
   }
   return set_background(f, Z, zdt, B, cols, stride, bias);
+}
+
+int ti_forest_set_quantiles(ti_forest* f, const double* q, int32_t n_q) {
+  if (!f) return fail(TI_ERR_INVALID, "null forest");
+  if (!q || n_q < 1 || n_q > ti::kQuantileMaxLevels)
+    return fail(TI_ERR_INVALID, "quantile levels: need 1 to " + std::to_string(ti::kQuantileMaxLevels));
+  for (int i = 0; i < n_q; ++i)
+    if (!(q[i] >= 0.0 && q[i] <= 1.0))
+      return fail(TI_ERR_INVALID, "quantile level " + std::to_string(i) + " is outside [0, 1]");
+  f->quant_q.assign(q, q + n_q);
+  return TI_OK;
 }
 
 int ti_forest_get_info(const ti_forest* f, ti_forest_info* info) {
@@ -1415,7 +1514,7 @@ int ti_forest_set_option(ti_forest* f, int32_t option, int64_t value) {
 int ti_output_shape(const ti_forest* f, int32_t kind, int64_t n_rows, int64_t* out_len,
                     int32_t* out_dtype) {
   if (!f || !out_len || !out_dtype) return fail(TI_ERR_INVALID, "null argument");
-  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_CONTRIB_INTERV) return fail(TI_ERR_INVALID, "bad output kind");
+  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_TREE_QUANTILE) return fail(TI_ERR_INVALID, "bad output kind");
   if (n_rows < 0) return fail(TI_ERR_INVALID, "negative n_rows");
   *out_len = n_rows * output_width(f, kind);
   *out_dtype = output_dtype(f, kind);
@@ -1426,7 +1525,7 @@ static int check_call(const ti_forest* f, const void* X, int32_t xdt, int64_t ro
                       int64_t stride, int32_t kind, const void* out, int64_t out_len) {
   if (!f) return fail(TI_ERR_INVALID, "null forest");
   if (xdt != TI_F32 && xdt != TI_F64) return fail(TI_ERR_INVALID, "x_dtype must be TI_F32 or TI_F64");
-  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_CONTRIB_INTERV) return fail(TI_ERR_INVALID, "bad output kind");
+  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_TREE_QUANTILE) return fail(TI_ERR_INVALID, "bad output kind");
   if (rows < 0) return fail(TI_ERR_INVALID, "negative n_rows");
   if (rows == 0) return TI_OK;
   if (!X || !out) return fail(TI_ERR_INVALID, "null data pointer");

@@ -293,6 +293,13 @@ struct ApproxPtrs {
   double* approx_bias = nullptr;             // [K]
 };
 
+// Tree-quantile tables (treeinfer_quantile.h: ensure_quantile)
+struct QuantilePtrs {
+  int64_t* quant_leaf_base = nullptr;   // [T + 1] first value of each tree
+  double* quant_values = nullptr;       // per (tree, leaf id) the leaf value
+  double* quant_weights = nullptr;      // [T]
+};
+
 // ti_predict scratch: device buffers + pinned host staging (grown x2)
 struct ScratchBufs {
   void* x_buf = nullptr;
@@ -342,13 +349,13 @@ struct CallScratch {
 // One replica.  Four groups of device memory, each a plain aggregate of
 // pointers (bases, so d.heap32 reads as before) reset by one assignment: the
 // forest's arrays, the TreeSHAP tables and the approximate-contribution
-// tables, freed from the record of what their uploads allocated (forest_mem /
-// shap_mem / approx_mem), and the scratch buffers, which grow() reallocates and
+// tables (and the tree-quantile tables beside them), freed from the record of
+// what their uploads allocated (forest_mem / shap_mem / approx_mem / quant_mem), and the scratch buffers, which grow() reallocates and
 // free_scratch frees.
-struct DeviceForest : ForestPtrs, ShapPtrs, ApproxPtrs, ScratchBufs {
+struct DeviceForest : ForestPtrs, ShapPtrs, ApproxPtrs, QuantilePtrs, ScratchBufs {
   int device = -1;
   hipStream_t stream = nullptr;
-  DeviceAllocs forest_mem, shap_mem, approx_mem;
+  DeviceAllocs forest_mem, shap_mem, approx_mem, quant_mem;
   std::atomic<int32_t> shap_tab_state{0};   // 0 not tried, 1 built, -1 failed or over the cap:
                                      // contributions use the extend / unwind kernel
   // TI_OUTPUT_INTERACT scratch (launch_interact: contributions + partials of
@@ -634,6 +641,19 @@ struct ti_forest {
     std::vector<double> leaf_value, cover, base_margin;
   };
   std::unique_ptr<ApproxSource> approx_src;
+  // Quantiles across trees (TI_OUTPUT_TREE_QUANTILE, treeinfer_quantile.h):
+  // quant_refused names why the forest cannot serve them (empty: it can).  The
+  // tables are built at create and uploaded on the first call (ensure_quantile,
+  // under shap_mu); the host copy goes once they are resident.  quant_q: the
+  // levels, written by ti_forest_set_quantiles with no call in flight.
+  std::string quant_refused;
+  std::atomic<bool> quant_ready{false};
+  struct QuantileTables {
+    std::vector<int64_t> leaf_base;
+    std::vector<double> values, weights;
+  };
+  std::unique_ptr<QuantileTables> quant_tab;
+  std::vector<double> quant_q{0.5};
   // Interventional contributions (TI_OUTPUT_CONTRIB_INTERV): rows of the
   // background set by ti_forest_set_background, 0 for none.  Written with no
   // call in flight, so calls read it without a lock.

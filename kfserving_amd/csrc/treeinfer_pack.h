@@ -68,6 +68,10 @@ int validate(const ti_forest_desc* d, std::vector<int>* depth_out) {
                   "pre-steps with linear leaves (the linear models would read the raw columns; no "
                   "loader produces the combination)");
   }
+  if (d->tree_weight)   // tree weights (ABI 11)
+    for (int t = 0; t < d->n_trees; ++t)
+      if (!(d->tree_weight[t] >= 0.0))
+        return fail(TI_ERR_INVALID, "tree_weight[" + std::to_string(t) + "] is negative or NaN");
   depth_out->assign(d->n_trees, 0);
   std::vector<int> stack_node, stack_depth;
   for (int t = 0; t < d->n_trees; ++t) {

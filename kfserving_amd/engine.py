@@ -19,9 +19,9 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .forest import (Forest, OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_CONTRIB_INTERV, OUT_INTERACT,
-                     OUT_LEAF, OUT_MARGIN, OUT_PREDICT, TI_F32, TI_F64, TI_I32)
+                     OUT_LEAF, OUT_MARGIN, OUT_PREDICT, OUT_TREE_QUANTILE, TI_F32, TI_F64, TI_I32)
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 _LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("TREEINFER_LIB", os.path.join(_LIB_DIR, "libtreeinfer.so"))
 
@@ -29,7 +29,7 @@ EXPORTED_SYMBOLS = (
     "ti_forest_create", "ti_forest_destroy", "ti_forest_get_info", "ti_output_shape",
     "ti_predict", "ti_predict_device", "ti_transform_device", "ti_last_error", "ti_device_count",
     "ti_abi_version", "ti_forest_set_option", "ti_pretransform_device",
-    "ti_forest_set_background",
+    "ti_forest_set_background", "ti_forest_set_quantiles",
 )
 
 # ti_forest_set_option options (include/treeinfer.h)
@@ -86,6 +86,7 @@ class _ForestDesc(ctypes.Structure):
         ("reserved1", ctypes.c_int32),
         ("pre_op", ctypes.c_void_p),
         ("pre_const", ctypes.c_void_p),
+        ("tree_weight", ctypes.c_void_p),
     ]
 
 
@@ -156,6 +157,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.ti_pretransform_device.argtypes = [vp, i32, vp, i32, i64, i32, i64, vp, vp]
         lib.ti_forest_set_background.restype = ctypes.c_int
         lib.ti_forest_set_background.argtypes = [vp, vp, i32, i64, i32, i64]
+        lib.ti_forest_set_quantiles.restype = ctypes.c_int
+        lib.ti_forest_set_quantiles.argtypes = [vp, vp, i32]
         if lib.ti_abi_version() != ABI_VERSION:
             raise TreeInferError(-1, f"ABI mismatch: library {lib.ti_abi_version()}, "
                                      f"binding {ABI_VERSION}")
@@ -259,11 +262,14 @@ class DeviceForest:
             desc.n_pre_steps = f.n_pre_steps
             desc.pre_op = _ptr(f.pre_ops)
             desc.pre_const = _ptr(f.pre_consts)
+        if f.tree_weight is not None:
+            desc.tree_weight = _ptr(f.tree_weight)
         dev_arr = (ctypes.c_int32 * len(devs))(*devs)
         handle = ctypes.c_void_p()
         _check(self._lib, self._lib.ti_forest_create(ctypes.byref(desc), dev_arr, len(devs),
                                                      ctypes.byref(handle)))
         self._handle = handle
+        self.quantiles = (0.5,)     # this handle's OUT_TREE_QUANTILE levels (set_quantiles)
 
     # ------------------------------------------------------------------ info
     def info(self) -> dict:
@@ -290,6 +296,18 @@ class DeviceForest:
         _check(self._lib, self._lib.ti_forest_set_background(self._handle, _ptr(Z) if rows else None,
                                                              zdt, rows, cols, cols))
 
+    def set_quantiles(self, q) -> None:
+        """ti_forest_set_quantiles: the levels OUT_TREE_QUANTILE answers, 1 to
+        8 of them in [0, 1]; its output is then [rows, len(q)] (one level: a
+        flat [rows], as OUT_PREDICT of one group).  Call it with no predict in
+        flight on this forest."""
+        levels = np.ascontiguousarray(np.atleast_1d(np.asarray(q, dtype=np.float64)))
+        if levels.ndim != 1:
+            raise ValueError(f"quantile levels must be a flat list, got shape {levels.shape}")
+        _check(self._lib, self._lib.ti_forest_set_quantiles(self._handle, _ptr(levels),
+                                                            int(levels.shape[0])))
+        self.quantiles = tuple(float(v) for v in levels)
+
     def linear_tile_rows(self, x_dtype) -> int:
         """Rows per tile of the linear-leaf pass (launch_linear in
         treeinfer.hip) for input of ``x_dtype``: the largest of 256 / 128 / 64
@@ -315,7 +333,7 @@ class DeviceForest:
     def predict(self, X, kind: int = OUT_PREDICT) -> np.ndarray:
         X = self.prepare_input(X)
         rows, cols = X.shape
-        width = self.forest.output_width(kind)
+        width = len(self.quantiles) if kind == OUT_TREE_QUANTILE else self.forest.output_width(kind)
         out = np.empty(rows * width, dtype=self.forest.output_dtype(kind))
         xdt = TI_F32 if X.dtype == np.float32 else TI_F64
         if rows:
@@ -382,5 +400,5 @@ class DeviceForest:
 __all__ = ["DeviceForest", "TreeInferError", "prepare_input", "load_library", "device_count", "default_devices",
            "OPT_SHAP_TABLE_ROWS", "OPT_SHAP_TABLE_MB", "OPT_HOST_REGISTER", "OPT_LINEAR_SCRATCH_MB",
            "EXPORTED_SYMBOLS", "OUT_MARGIN", "OUT_PREDICT", "OUT_LEAF", "OUT_CONTRIB", "OUT_INTERACT",
-           "OUT_CONTRIB_APPROX", "OUT_CONTRIB_INTERV",
+           "OUT_CONTRIB_APPROX", "OUT_CONTRIB_INTERV", "OUT_TREE_QUANTILE",
            "TI_F32", "TI_F64", "TI_I32"]

@@ -48,6 +48,9 @@ OUT_CONTRIB = 3     # TreeSHAP contributions [rows, K * (F + 1)], bias last per 
 OUT_INTERACT = 4    # SHAP interaction values [rows, K * (F + 1) * (F + 1)] (pred_interactions)
 OUT_CONTRIB_APPROX = 5   # approximate (Saabas) contributions, laid out as OUT_CONTRIB (approx_contribs)
 OUT_CONTRIB_INTERV = 6   # interventional TreeSHAP against a background set, laid out as OUT_CONTRIB
+OUT_TREE_QUANTILE = 7    # weighted quantiles of a row's per-tree predictions [rows, n_q]
+TREE_QUANTILE_MAX_TREES = 4096     # the kernel's cap (treeinfer_quantile.h)
+TREE_QUANTILE_MAX_LEVELS = 8
 
 # pre-step operations (treeinfer.h TI_PRE_*)
 PRE_FILL_NAN = 0
@@ -122,6 +125,11 @@ class Forest:
     # forest has none
     pre_ops: Optional[np.ndarray] = None        # int32 [S]
     pre_consts: Optional[np.ndarray] = None     # float64 [S, F]
+    # tree weights (AdaBoostRegressor.estimator_weights_): read by
+    # OUT_TREE_QUANTILE alone, which orders a row's per-tree predictions and
+    # answers the value where the cumulative weight reaches q of the total
+    # (include/treeinfer.h).  None: every weight is 1
+    tree_weight: Optional[np.ndarray] = None    # float64 [T]
     library: str = ""
     objective: str = ""
     feature_names: Optional[List[str]] = None
@@ -213,6 +221,13 @@ class Forest:
             if np.any(self.cat_offset[cat] < 0) or np.any(end > self.cat_bits.shape[0]):
                 raise ValueError("categorical bitset out of range")
 
+        if self.tree_weight is not None:
+            w = np.asarray(self.tree_weight)
+            if w.shape != (T,):
+                raise ValueError(f"tree_weight must be [n_trees], got shape {w.shape}")
+            if not np.all(w >= 0):     # NaN fails the comparison too
+                raise ValueError("tree_weight must be >= 0 and not NaN")
+
         if (self.pre_ops is None) != (self.pre_consts is None):
             raise ValueError("pre-steps need pre_ops and pre_consts")
         if self.pre_ops is not None:
@@ -274,6 +289,8 @@ class Forest:
         if self.pre_ops is not None:
             self.pre_ops = np.ascontiguousarray(self.pre_ops, dtype=np.int32)
             self.pre_consts = np.ascontiguousarray(self.pre_consts, dtype=np.float64)
+        if self.tree_weight is not None:
+            self.tree_weight = np.ascontiguousarray(self.tree_weight, dtype=np.float64)
         return self
 
     def tree_subset(self, t0: int, t1: int, keep_base: bool = True) -> "Forest":
@@ -299,6 +316,8 @@ class Forest:
             feature=cut(self.feature), threshold=cut(self.threshold), flags=cut(self.flags),
             left=cut(self.left), right=cut(self.right), leaf_id=cut(self.leaf_id),
             leaf_value=cut(self.leaf_value), cover=cut(self.cover),
+            tree_weight=(None if self.tree_weight is None
+                         else np.ascontiguousarray(self.tree_weight[t0:t1])),
             cat_offset=cut(self.cat_offset), cat_nwords=cut(self.cat_nwords),
             base_margin=(self.base_margin.copy() if keep_base
                          else np.zeros_like(self.base_margin)),
@@ -315,6 +334,8 @@ class Forest:
             return self.n_groups * (self.n_features + 1)
         if kind == OUT_INTERACT:
             return self.n_groups * (self.n_features + 1) ** 2
+        if kind == OUT_TREE_QUANTILE:   # as many as the device handle has levels
+            raise ValueError("OUT_TREE_QUANTILE's width is DeviceForest.quantiles', not the forest's")
         if kind == OUT_PREDICT and self.transform == T_ARGMAX:
             return 1
         return self.n_groups

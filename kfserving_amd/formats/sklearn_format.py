@@ -6,7 +6,8 @@ python/sklearnserver/sklearnserver/model.py:38 (``joblib.load``) and calls at
 RandomForest{Regressor,Classifier}, ExtraTrees{Regressor,Classifier} with one
 output, GradientBoosting{Regressor,Classifier} (forest_from_gradient_boosting)
 and HistGradientBoosting{Regressor,Classifier}
-(forest_from_hist_gradient_boosting), and a Pipeline of SimpleImputer /
+(forest_from_hist_gradient_boosting), AdaBoost{Regressor,Classifier} over
+tree members (forest_from_adaboost), and a Pipeline of SimpleImputer /
 StandardScaler / MinMaxScaler / MaxAbsScaler / RobustScaler steps in front of
 any of these but HistGradientBoosting (forest_from_pipeline).
 
@@ -30,7 +31,7 @@ from typing import Tuple
 
 import numpy as np
 
-from ..forest import (Forest, NODE_NAN_LEFT, PRE_ADD, PRE_DIV, PRE_FILL_NAN, PRE_MAX_STEPS, PRE_MUL,
+from ..forest import (Forest, NODE_NAN_LEFT, OUT_TREE_QUANTILE, TREE_QUANTILE_MAX_TREES, PRE_ADD, PRE_DIV, PRE_FILL_NAN, PRE_MAX_STEPS, PRE_MUL,
                       PRE_SUB, TI_F32, TI_F64, T_ARGMAX, T_EXP, T_HINGE, T_IDENTITY, T_STEP,
                       concat_trees)
 
@@ -102,6 +103,9 @@ def _estimators(est) -> Tuple[list, bool]:
     if name in ("DecisionTreeRegressor", "DecisionTreeClassifier", "ExtraTreeRegressor",
                 "ExtraTreeClassifier"):
         return [est], False
+    if name in ("AdaBoostRegressor", "AdaBoostClassifier"):
+        raise TypeError(f"sklearn estimator {name} has no tree-array (.npz) export: its trees "
+                        "carry weights the export does not hold; save it with joblib")
     raise TypeError(f"sklearn estimator {name} is not a supported tree ensemble "
                     "(RandomForest / ExtraTrees / DecisionTree)")
 
@@ -159,6 +163,82 @@ def forest_from_gradient_boosting(est) -> Forest:
         input_dtype=TI_F32, library="sklearn", objective=type(est).__name__,
         meta={"classes": np.asarray(est.classes_) if classifier else None,
               "allow_nan": False},
+    ).contiguous()
+
+
+def forest_from_adaboost(est) -> Forest:
+    """AdaBoost{Regressor,Classifier} over decision-tree members (installed
+    sklearn 1.7.2, ensemble/_weight_boosting.py).  X is converted to float32 by
+    each member and NaN is rejected by the ensemble's own check.
+
+    Regressor (``_get_median_predict``): the weighted median of the members'
+    predictions -- order them, cumulate ``estimator_weights_`` in that order
+    (numpy's sequential float64 cumsum) and take the first at or above half the
+    total.  No sum of trees says that: the forest carries the weights as
+    ``tree_weight`` and names OUT_TREE_QUANTILE, whose default level is 0.5, as
+    its prediction (``meta["predict_kind"]``); the leaf payload is
+    ``value[leaf]``.  The engine breaks ties of equal predictions by tree index
+    where numpy's argsort leaves them unspecified: tied members predict the
+    same value, so only a cumulative weight within rounding of half the total
+    inside a tie could tell (include/treeinfer.h).
+
+    Classifier (SAMME, ``decision_function``): member i adds ``w_i`` to the
+    class it predicts and ``-1 / (K - 1) * w_i`` to the others, summed in
+    member order in float64 and divided by ``estimator_weights_.sum()``: vector
+    leaves holding exactly those doubles at the leaf's first-argmax class, the
+    divisor, first argmax (for K = 2 sklearn's ``(-p0) + p1 > 0`` is the same
+    choice).  OUT_MARGIN of K >= 3 classes is ``decision_function``."""
+    name = type(est).__name__
+    members = list(est.estimators_)
+    if not members:
+        raise TypeError(f"{name} has no fitted members")
+    classifier = name == "AdaBoostClassifier"
+    want = (("DecisionTreeClassifier", "ExtraTreeClassifier") if classifier
+            else ("DecisionTreeRegressor", "ExtraTreeRegressor"))
+    for i, m in enumerate(members):
+        if type(m).__name__ not in want:
+            raise TypeError(f"{name} member {i} is a {type(m).__name__}: only decision-tree base "
+                            f"estimators ({' / '.join(want)}) are supported")
+        if getattr(m, "n_outputs_", 1) != 1:
+            raise TypeError(f"{name} member {i} has {m.n_outputs_} outputs: multi-output "
+                            "members are not supported")
+    weights = np.asarray(est.estimator_weights_, dtype=np.float64)
+    F = int(est.n_features_in_)
+    arrays = [tree_arrays_from_sklearn(m.tree_) for m in members]
+    if not classifier:
+        if len(members) > TREE_QUANTILE_MAX_TREES:
+            raise TypeError(f"{name} has {len(members)} members, the weighted median is served "
+                            f"for at most {TREE_QUANTILE_MAX_TREES}")
+        forest = forest_from_tree_arrays(arrays, F, False, average=False, kind=name)
+        forest.tree_weight = weights[:len(members)].copy()
+        forest.meta.update(allow_nan=False, predict_kind=OUT_TREE_QUANTILE)
+        return forest.contiguous()
+    K = int(est.n_classes_)
+    if K == 1:
+        raise TypeError(f"{name} fitted on one class is not supported")
+    classes = np.asarray(est.classes_)
+    canon = []
+    for i, (m, arr, w) in enumerate(zip(members, arrays, weights)):
+        if not np.array_equal(np.asarray(m.classes_), classes):
+            raise TypeError(f"{name} member {i} was fitted on classes {np.asarray(m.classes_)}, "
+                            f"the ensemble on {classes}")
+        t = _canon_tree(arr, True, K)
+        leaf = t["feature"] < 0
+        votes = np.full((leaf.shape[0], K), -1 / (K - 1) * w)       # decision_function's doubles
+        votes[np.arange(leaf.shape[0]), np.argmax(arr["value"][:, 0, :K], axis=1)] = w
+        t["leaf_value"] = np.where(leaf[:, None], votes, 0.0)
+        canon.append(t)
+    cat = concat_trees(canon, K)
+    return Forest(
+        n_features=F, n_groups=K, leaf_width=K, accum_dtype=TI_F64,
+        base_first=True, lgb_zero_map=False,
+        tree_offset=cat["tree_offset"], tree_group=np.zeros(len(members), dtype=np.int32),
+        feature=cat["feature"], threshold=cat["threshold"], flags=cat["flags"],
+        left=cat["left"], right=cat["right"], leaf_id=cat["leaf_id"],
+        leaf_value=cat["leaf_value"], base_margin=np.zeros(K), cover=cat["cover"],
+        average_divisor=float(weights.sum()), transform=T_ARGMAX, transform_param=1.0,
+        input_dtype=TI_F32, library="sklearn", objective=name,
+        meta={"classes": classes, "allow_nan": False},
     ).contiguous()
 
 
@@ -471,6 +551,8 @@ def forest_from_sklearn(est) -> Forest:
         return forest_from_hist_gradient_boosting(est)
     if type(est).__name__ in ("GradientBoostingRegressor", "GradientBoostingClassifier"):
         return forest_from_gradient_boosting(est)
+    if type(est).__name__ in ("AdaBoostRegressor", "AdaBoostClassifier"):
+        return forest_from_adaboost(est)
     members, average = _estimators(est)
     if getattr(est, "n_outputs_", 1) != 1:
         raise ValueError("multi-output sklearn models are not supported")

@@ -339,8 +339,12 @@ class Application:
         """predict -> postprocess, through the batcher when one is configured:
         ``instances`` as they are, lgbserver ``inputs`` as the float64 matrix
         their columns select (``batch_inputs``), one batcher per model and
-        request kind."""
-        if self._batcher_factory is not None and isinstance(request, dict):
+        request kind.  A batch carries rows alone, so a request with a key
+        that changes what its model answers (``model.unbatched_request_keys``:
+        sklearnserver's ``"quantiles"``) goes to ``model.predict`` by itself."""
+        alone = isinstance(request, dict) and any(
+            k in request for k in getattr(model, "unbatched_request_keys", ()))
+        if self._batcher_factory is not None and isinstance(request, dict) and not alone:
             chunk, kind = None, None
             if "instances" in request:
                 chunk, kind = request["instances"], "instances"

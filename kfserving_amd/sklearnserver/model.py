@@ -5,7 +5,7 @@ finds model.joblib / .pkl / .pickle like the reference (:21-41; these files
 are the user's own model, loaded with joblib exactly as the reference does)
 or the pickle-free ``model.npz`` tree-array export, and flattens a
 RandomForest / ExtraTrees / DecisionTree / GradientBoosting /
-HistGradientBoosting estimator, or a Pipeline of imputer / scaler steps in
+HistGradientBoosting / AdaBoost estimator, or a Pipeline of imputer / scaler steps in
 front of one (its steps run on the device as the forest's pre-steps);
 ``predict`` runs the trees through
 libtreeinfer where the reference called ``_model.predict``.
@@ -19,6 +19,7 @@ from ..formats.sklearn_format import forest_from_sklearn, load_tree_arrays
 from ..kfserving.kfmodel import KFModel
 from ..kfserving.storage import Storage
 from ..engine import prepare_input
+from ..forest import OUT_TREE_QUANTILE, TREE_QUANTILE_MAX_LEVELS, TREE_QUANTILE_MAX_TREES
 from ..tree_model import GPUForestMixin
 
 MODEL_BASENAME = "model"
@@ -27,6 +28,10 @@ ARRAYS_EXTENSION = ".npz"
 
 
 class SKLearnModel(GPUForestMixin, KFModel):  # pylint:disable=c-extension-no-member
+    # request keys beside "instances" that change the answer: KFServer sends
+    # such a request to predict() alone, never through a batcher
+    unbatched_request_keys = ("quantiles",)
+
     def __init__(self, name: str, model_dir: str, background=None):
         super().__init__(name)
         self.name = name
@@ -201,6 +206,8 @@ class SKLearnModel(GPUForestMixin, KFModel):  # pylint:disable=c-extension-no-me
         f = self._forest
         if f is None or f.meta.get("hist_gradient_boosting") or f.meta.get("pipeline"):
             return None   # a Pipeline's checks (_pipeline_matrix) are the application's too
+        if f.objective in ("AdaBoostRegressor", "AdaBoostClassifier"):
+            return None   # the regressor's answer is no OUT_PREDICT; both keep the one route
         return (1 << 8) | (0 if f.meta.get("allow_nan", True) else (1 << 9))
 
     @property
@@ -213,6 +220,36 @@ class SKLearnModel(GPUForestMixin, KFModel):  # pylint:disable=c-extension-no-me
         if f is None or f.meta.get("classes") is not None:
             return None
         return self.native_v1_transform
+
+    @property
+    def native_batching(self):
+        """The native batcher sends its batches straight to OUT_PREDICT; a
+        forest that predicts by another kind (an AdaBoostRegressor's weighted
+        median) keeps the asyncio batcher, which calls :meth:`predict`."""
+        f = self._forest
+        return f is None or "predict_kind" not in f.meta
+
+    def quantile_levels(self, request: Dict):
+        """The request's optional ``"quantiles": [q, ...]`` key, checked: None
+        when absent.  Served for an AdaBoostRegressor (its members' weights)
+        and for a regressor that averages scalar-leaf trees (RandomForest /
+        ExtraTrees / DecisionTree; every weight 1)."""
+        if not isinstance(request, dict) or "quantiles" not in request:
+            return None
+        f = self._forest
+        ok = f.meta.get("predict_kind") == OUT_TREE_QUANTILE or f.objective in (
+            "RandomForestRegressor", "ExtraTreesRegressor", "DecisionTreeRegressor",
+            "ExtraTreeRegressor")
+        if not ok or f.n_trees > TREE_QUANTILE_MAX_TREES:
+            raise ValueError('"quantiles" is served for AdaBoostRegressor and for RandomForest / '
+                             "ExtraTrees / DecisionTree regressors of at most %d trees, not for "
+                             "this %s" % (TREE_QUANTILE_MAX_TREES, f.objective or "model"))
+        q = np.asarray(request["quantiles"], dtype=np.float64)
+        if q.ndim != 1 or not 1 <= q.shape[0] <= TREE_QUANTILE_MAX_LEVELS or \
+                not np.all((q >= 0) & (q <= 1)):
+            raise ValueError('"quantiles" must be a list of 1 to %d levels in [0, 1]'
+                             % TREE_QUANTILE_MAX_LEVELS)
+        return q
 
     def native_v1_labels(self):
         """A classifier's labels as its predict renders them
@@ -238,7 +275,12 @@ class SKLearnModel(GPUForestMixin, KFModel):  # pylint:disable=c-extension-no-me
         inputs = self._array(request)
         try:
             f = self._forest
-            result = self.predict_matrix(self.request_matrix({"instances": inputs}))
+            levels = self.quantile_levels(request)
+            X = self.request_matrix({"instances": inputs})
+            if levels is not None:      # [rows][n_q], one level included
+                result = self.predict_quantiles(X, levels).reshape(X.shape[0], levels.shape[0])
+                return {"predictions": result.tolist()}
+            result = self.predict_matrix(X)
             classes = f.meta.get("classes")
             if classes is not None:
                 result = np.asarray(classes).take(result.astype(np.int64), axis=0)

@@ -17,7 +17,7 @@ import numpy as np
 
 from .engine import DeviceForest, prepare_input
 from .forest import (OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_CONTRIB_INTERV, OUT_INTERACT, OUT_PREDICT,
-                     Forest)
+                     OUT_TREE_QUANTILE, Forest)
 
 BACKGROUND_FILE = "background.npy"
 
@@ -72,7 +72,26 @@ class GPUForestMixin:
         return dfo
 
     def predict_matrix(self, X: np.ndarray, kind: int = OUT_PREDICT) -> np.ndarray:
+        """One batch through the device forest.  A forest whose prediction is
+        not its transformed sum names the kind that is in ``meta["predict_kind"]``
+        (an AdaBoostRegressor: OUT_TREE_QUANTILE, the weighted median), and a
+        caller that asked for OUT_PREDICT gets that."""
+        if kind == OUT_PREDICT and self._forest is not None:
+            kind = self._forest.meta.get("predict_kind", OUT_PREDICT)
+        if kind == OUT_TREE_QUANTILE:
+            return self.predict_quantiles(X, (0.5,))
         return self.device_forest().predict(X, kind)
+
+    def predict_quantiles(self, X: np.ndarray, levels) -> np.ndarray:
+        """OUT_TREE_QUANTILE at ``levels``: [rows] for one level, else [rows,
+        len(levels)].  The levels are the device forest's own state, so every
+        quantile call of a model takes one lock around setting them and
+        predicting."""
+        dev = self.device_forest()
+        with self._dev_lock:
+            if dev.quantiles != tuple(float(v) for v in levels):
+                dev.set_quantiles(levels)
+            return dev.predict(X, OUT_TREE_QUANTILE)
 
     # V2 tensors (kfserving.v2): a [rows, features] numeric matrix, read with
     # the numpy-argument semantics of each library (NaN = missing)
