@@ -334,9 +334,10 @@ typedef struct ti_forest_info {
                                  staged records, 10 categorical heap (LDS-staged, the
                                  bitsets inside each tree's block), 11 categorical
                                  records (layout 7 with category codes in the bin image
-                                 and each tree's bitset runs staged behind its records)
-                                 (2, 4 and 5 were retired in
-                                 round 3)                                            */
+                                 and each tree's bitset runs staged behind its records),
+                                 12 oblivious trees (a descriptor a level, a leaf table
+                                 a tree; recognised at pack time) (DESIGN.md section 3;
+                                 2, 4 and 5 were retired in round 3)                 */
   int32_t depth;              /* heap depth D, or max depth for explicit             */
   int32_t n_trees;
   int32_t n_groups;
@@ -350,7 +351,7 @@ typedef struct ti_forest_info {
                                  scalar-loaded root                                  */
   int32_t bin_bits;           /* 8 or 16: bin width of the float32 image (0: none)   */
   int32_t tree_ilp;           /* record layouts: trees walked at once per lane       */
-  int32_t n_stages;           /* staged layouts (7, 9, 10, 11): LDS stages of the forest
+  int32_t n_stages;           /* staged layouts (7, 9, 10, 11, 12): LDS stages of the forest
                                  (10: of a float32 batch)                            */
   int32_t top_depth;          /* layouts 8, 9: levels of each tree's heap top        */
   int32_t bottom;             /* layout 9: 0 records, 1 compact u8 nodes (plan_tx8),

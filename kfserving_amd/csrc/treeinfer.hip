@@ -85,6 +85,19 @@ int upload_device(const ti_forest* f, DeviceForest& d, int device) {
     up(&d.heap32, h.heap32);
     up(&d.heap64, h.heap64);
     up(&d.heap_leaf_ids, h.heap_leaf_ids);
+  } else if (L == kLayoutOblivious) {
+    for (int i = 0; i < 2; ++i) {
+      up(&d.ob_desc[i], h.rec.ob_desc[i]);
+      up(&d.bx_tbl[i], h.rec.rx[i].tbl);
+    }
+    up(&d.ob_first, h.rec.ob_first);
+    up(&d.ob_goff, h.rec.ob_goff);
+    up(&d.ob_img, h.rec.ob_img);
+    up(&d.rx_base, h.rx_base);   // each tree's byte in the image's staged part
+    up(&d.rx_nint, h.rx_nint);   // its depth, bit 31: gathered
+    up(&d.lx_stage, h.rec.lx_stage);
+    up(&d.leaf_base, h.leaf_base);
+    up(&d.exp_leaf_ids, h.exp_leaf_ids);
   } else if (is_record(L)) {
     // 6-8 walk the records (8: below a heap top); 9 walks [top | bottom] images
     // and takes rx_base / rx_nint from the tx arrays
@@ -381,6 +394,31 @@ int plan_launch(const ti_forest* f, const DeviceForest& d, int xdt, int kind, La
       if (d.bh_fix_img != nullptr) a.trees = d.bh_fix_img;   // same walk, hot pair slots first
       p->lds = ti::fix_lds_bytes(kmax, ng, f->T);
     }
+  } else if (f->layout == kLayoutOblivious) {
+    // [bin image][flag][two stage buffers of lx_stage_cap bytes, also the binning temp]
+    const RecPlan& rx = f->rx[ii];
+    a.rx_base = d.rx_base;
+    a.rx_nint = d.rx_nint;
+    a.leaf_base = d.leaf_base;
+    a.exp_leaf_ids = d.exp_leaf_ids;
+    a.bin_tbl = d.bx_tbl[ii];
+    a.bin_L = rx.L;
+    a.bin_kary = rx.kary;
+    a.bin_words = rx.words;
+    a.trees = d.ob_img;
+    a.tree_stride = f->lx_stage_cap;
+    a.ob_desc = d.ob_desc[ii];
+    a.ob_first = d.ob_first;
+    a.ob_goff = d.ob_goff;
+    a.stage_start = d.lx_stage;
+    a.n_stages = f->n_stages;
+    a.stage_off = static_cast<int32_t>(align16(t.feat_bytes + 4));
+    const size_t area = 2 * static_cast<size_t>(f->lx_stage_cap);
+    p->lds = static_cast<size_t>(a.stage_off) + area;
+    if (p->lds > kLdsPerCu || static_cast<int64_t>(kLxPf) * 16 * R < f->lx_stage_cap)
+      return fail(TI_ERR_UNSUPPORTED, "oblivious layout exceeds LDS");
+    a.bin_chunk = bin_chunk_for(area, R, xdt, f->F);
+    key.walk = f->ob_gather ? ti::Walk::ObliviousGather : ti::Walk::Oblivious;
   } else if (is_record(f->layout)) {
     // record layouts: [bin image][flag][stage area (7, 8, 9)]
     const RecPlan& rx = f->rx[ii];

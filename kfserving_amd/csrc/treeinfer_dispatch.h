@@ -1,8 +1,8 @@
 // treeinfer_dispatch.h — kernel selection across the translation units.  Each
 // treeinfer_k_<x><a>.hip instantiates every kernel of one (input type,
-// accumulator type) pair, treeinfer_k_cat.hip the categorical heap's and
-// treeinfer_k_crec.hip the categorical records' for all four pairs, so the six
-// compile in parallel.
+// accumulator type) pair, treeinfer_k_cat.hip the categorical heap's,
+// treeinfer_k_crec.hip the categorical records' and treeinfer_k_obliv.hip the
+// oblivious trees' for all four pairs, so the seven compile in parallel.
 //
 // The host names what it launches with a KernelKey; ti::select(key) is the one
 // way from a key to a kernel.  Each rule that turns a runtime value into a
@@ -36,6 +36,8 @@ enum class Walk {
   CatHeapLgb,       // 10: categorical heap, LightGBM's rule  (treeinfer_cheap.h)
   CatRecordXgb,     // 11: categorical records, XGBoost's rule   crexplicit_predict_kernel
   CatRecordLgb,     // 11: categorical records, LightGBM's rule  (treeinfer_crec.h)
+  Oblivious,        // 12: oblivious trees, every table staged   oblivious_predict_kernel
+  ObliviousGather,  // 12: ... some tables gathered              (treeinfer_obliv.h)
 };
 
 struct KernelKey {
@@ -138,6 +140,9 @@ KernelFn select_walk(const KernelKey& k) {
     case Walk::CatRecordXgb:
     case Walk::CatRecordLgb:
       break;   // kernels_crec
+    case Walk::Oblivious:
+    case Walk::ObliviousGather:
+      break;   // kernels_obliv
   }
   return nullptr;
 }
@@ -155,10 +160,12 @@ KernelFn kernels_dd(const KernelKey& k);    // double X, double acc
 KernelFn kernels_df(const KernelKey& k);    // double X, float acc
 KernelFn kernels_cat(const KernelKey& k);   // the categorical heap, every pair
 KernelFn kernels_crec(const KernelKey& k);  // the categorical records, every pair
+KernelFn kernels_obliv(const KernelKey& k); // the oblivious trees, every pair
 
 inline KernelFn select(const KernelKey& k) {
   if (k.walk == Walk::CatHeapXgb || k.walk == Walk::CatHeapLgb) return kernels_cat(k);
   if (k.walk == Walk::CatRecordXgb || k.walk == Walk::CatRecordLgb) return kernels_crec(k);
+  if (k.walk == Walk::Oblivious || k.walk == Walk::ObliviousGather) return kernels_obliv(k);
   if (!k.x64) return k.acc64 ? kernels_fd(k) : kernels_ff(k);
   return k.acc64 ? kernels_dd(k) : kernels_df(k);
 }

@@ -190,16 +190,21 @@ enum Layout : int32_t {
   kLayoutCatHeap = 10,    // categorical heap (the heap's fields)
   kLayoutCatRecord = 11,  // layout 7 for categorical forests: category codes in the bin
                           //   image, each tree's bitset runs staged behind its records
+  kLayoutOblivious = 12,  // oblivious trees: per level one wave-uniform descriptor, per
+                          //   tree a leaf table staged in LDS (treeinfer_obliv.h)
 };
 // the record family: binned features, rx[] plans, the leaf tables of layout 1
 constexpr bool is_record(int32_t l) {
-  return (l >= kLayoutRecord && l <= kLayoutTopStaged) || l == kLayoutCatRecord;
+  return (l >= kLayoutRecord && l <= kLayoutTopStaged) || l == kLayoutCatRecord ||
+         l == kLayoutOblivious;   // 12 has the bin image and rx[] plans, and leaf tables of its own
 }
 // a heap top of hx_top levels in LDS
 constexpr bool has_heap_top(int32_t l) { return l == kLayoutHeapTop || l == kLayoutTopStaged; }
 // whole trees staged in LDS: lx_stage / lx_stage_cap / lx_ilp / n_stages
+// (12: leaf tables, lx_stage_cap the bytes of one of its two stage buffers)
 constexpr bool stages_trees(int32_t l) {
-  return l == kLayoutStaged || l == kLayoutTopStaged || l == kLayoutCatRecord;
+  return l == kLayoutStaged || l == kLayoutTopStaged || l == kLayoutCatRecord ||
+         l == kLayoutOblivious;
 }
 // the heap's fields: stride32/64, rows32/64, heap32/64 images
 constexpr bool heap_fields(int32_t l) { return l == kLayoutHeap || l == kLayoutCatHeap; }
@@ -264,6 +269,12 @@ struct ForestPtrs {
   int32_t* tx8_ord = nullptr;    //   leaf ordinal per bottom position
   uint32_t* hx_top[2] = {nullptr, nullptr};   // heap tops of layouts 8 and 9, per input dtype
   int32_t* cat_limit = nullptr;  // layout 11: per feature the category code limit, -1 numerical
+  // layout 12 (treeinfer_obliv.h): level descriptors per input dtype, each tree's first
+  // descriptor, the leaf-table image and where a gathered tree's table starts in it
+  uint32_t* ob_desc[2] = {nullptr, nullptr};
+  uint32_t* ob_first = nullptr;
+  unsigned char* ob_img = nullptr;
+  uint32_t* ob_goff = nullptr;
   // linear leaves (treeinfer_linear.h): leaf records, their terms, first record of each tree
   ti::LinLeaf* lin_leaves = nullptr;
   ti::LinTerm* lin_terms = nullptr;
@@ -507,6 +518,13 @@ struct RecArrays {
   std::vector<int32_t> tx8_ord;
   // layout 11: per feature L_f = 32 x its longest bitset in words, -1 for a numerical feature
   std::vector<int32_t> cat_limit;
+  // layout 12 (plan_oblivious): per view the 32-bit level descriptors, least significant
+  // level of each tree first, padded to an even count a tree; per tree its first
+  // descriptor; the leaf tables ([2^D][leaf_width] ACC a tree, 16-byte aligned: the staged
+  // ones first, then the gathered ones); per tree the 16-byte word where a gathered tree's
+  // table starts (0: staged)
+  std::vector<uint32_t> ob_desc[2], ob_first, ob_goff;
+  std::vector<unsigned char> ob_img;
 };
 
 // Every packed array that exists only to be uploaded.  The forest owns one
@@ -584,6 +602,7 @@ struct ti_forest {
   int32_t tx8 = 0;                 // 1: compact u8 bottom, 2: compact u16 bottom, 3: the u16
                                    //   bottom walked two lanes a row (t16split_predict_kernel)
   uint32_t tx16_mask = 0;          //   u16: the bottom word's bin-offset bits (KArgs bin_mask)
+  int32_t ob_gather = 0;           // layout 12: some tree's leaf table is gathered, not staged
   // ---- the packed arrays, until every replica is resident
   std::unique_ptr<HostImage> host;
   // TreeSHAP (TI_OUTPUT_CONTRIB); has_shap = 0 when the forest has no covers

@@ -130,6 +130,12 @@ struct KArgs {
   // categorical records (11), last so that every other field keeps its offset:
   // per feature the code limit L_f, -1 for a numerical feature
   const int32_t* cat_limit;       // [F]
+  // oblivious trees (12, treeinfer_obliv.h), after it for the same reason.  The
+  // leaf-table image is `trees`, rx_base each tree's byte in it, rx_nint its
+  // depth (bit 31: gathered), tree_stride the bytes of one stage buffer.
+  const uint32_t* ob_desc;        // level descriptors, a tree's least significant level first
+  const uint32_t* ob_first;       // [T] first descriptor of each tree
+  const uint32_t* ob_goff;        // [T] 16-byte word of a gathered tree's table in `trees`
 };
 
 __device__ __forceinline__ size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
@@ -1587,6 +1593,11 @@ constexpr uint32_t kRxOffMask = 0xFFFAu;   // the bin byte offset without the fl
 // half the byte offset of its bitset run in the tree's block, not a rank.
 constexpr uint32_t kCrCat = 8u;
 constexpr uint32_t kCrOffMask = 0xFFF2u;   // kRxOffMask without kCrCat
+// Oblivious trees (layout 12, treeinfer_obliv.h).  A pad level: rank 0xFFFF is
+// below no bin, and NaN-left sends the NaN code (0xFFFF, tiles on the slow
+// step) left as well; it reads the lane's bin 0.
+constexpr uint32_t kObPad = 0xFFFF0000u | kRxNanLeft;
+constexpr uint32_t kObGather = 0x80000000u;   // rx_nint: the tree's table is not staged
 // The bin of a categorical column: the category code both rules read, with
 // every value that "goes where non-members go" folded into the limit `lim`
 // (= 32 x the longest bitset on the feature, in words; the runs end in a zero

@@ -1562,6 +1562,200 @@ int pack_linear(const ti_forest_desc* d, HostImage* h) {
   return TI_OK;
 }
 
+// ------------------------------------------------ oblivious trees (layout 12)
+// A forest is oblivious when it has no categorical node, no linear leaf and no
+// zero-missing rule, every tree is complete to its own depth (<= kObMaxDepth;
+// depths may differ, 0 included) and all nodes of a level of a tree share
+// feature, threshold and flags.  ob_levels says so for one tree and returns
+// one node of each level, root first, and the leaves left to right: the leaf
+// at position p is reached by going right at level l iff bit D - 1 - l of p is
+// set, so descriptor j of a tree (bit j of the index) is level D - 1 - j.
+constexpr int kObMaxDepth = 16;
+// A table is staged while it is at most this many bytes (and fits a buffer):
+// at 256-row tiles two 16-byte words a thread.  Staging a table of W words
+// costs a wave W / R coalesced 16-byte loads (a 1 KB request each) and as many
+// LDS writes; gathering its leaf instead costs one request of 64 scattered
+// lines.  By the texture path's line rate that breaks even near W = 2.7 R
+// (reasoned, not measured).  float64 scalar leaves: depth <= 10
+// staged, 11 to 16 gathered; float32 scalar: <= 11; three float64 a leaf: <= 8.
+constexpr size_t kObStageMax = 8192;
+
+bool ob_levels(const ti_forest_desc* d, int t, std::vector<int64_t>* level_node,
+               std::vector<int64_t>* leaf_at) {
+  const int64_t b = d->tree_offset[t];
+  std::vector<int64_t> cur(1, b), next;
+  level_node->clear();
+  for (;;) {
+    const int64_t g0 = cur[0];
+    const bool leaf = d->feature[g0] < 0;
+    for (const int64_t g : cur) {
+      if ((d->feature[g] < 0) != leaf) return false;
+      if (!leaf && (d->feature[g] != d->feature[g0] || d->flags[g] != d->flags[g0] ||
+                    std::memcmp(&d->threshold[g], &d->threshold[g0], sizeof(double)) != 0))
+        return false;
+    }
+    if (leaf) break;
+    if (static_cast<int>(level_node->size()) == kObMaxDepth) return false;
+    level_node->push_back(g0);
+    next.clear();
+    for (const int64_t g : cur) {
+      next.push_back(b + d->left[g]);
+      next.push_back(b + d->right[g]);
+    }
+    cur.swap(next);
+  }
+  *leaf_at = std::move(cur);
+  return true;
+}
+
+// Bytes of one of the two stage buffers for tiles of R rows under a bin image
+// of `words` words a row: what a quarter of the CU's LDS leaves (four
+// workgroups, 16 waves a CU at 256 rows), or a third, a half, all of it while
+// that is less than the largest staged table; within the prefetch registers.
+size_t ob_stage_cap(int words, int R) {
+  const size_t bins = align16(static_cast<size_t>(words) * R * 4 + 4);
+  size_t cap = 0;
+  for (int wgs = 4; wgs >= 1; --wgs) {
+    const size_t share = kLdsPerCu / static_cast<size_t>(wgs);
+    cap = share > bins ? ((share - bins) / 2) & ~size_t(15) : 0;
+    cap = std::min(cap, static_cast<size_t>(kLxPf) * 16 * R);
+    if (cap >= kObStageMax) break;
+  }
+  return cap;
+}
+
+// The bin plan, search tables and descriptors of one input view (ranks differ
+// between the views): pack_rexplicit's u16 image, no records.
+template <typename XT>
+bool pack_ob_view(const ti_forest_desc* d, const std::vector<std::vector<int64_t>>& levels,
+                  RecExplicit* out, std::vector<uint32_t>* desc) {
+  const RankTables<XT> rt = collect_ranks<XT>(d, false);
+  if (rt.m_max > 65533u) return false;
+  RecExplicit view;
+  view.b8 = 0;
+  view.words = (d->n_features + 1) / 2;
+  int R = 64;
+  const int want_rows = env_int("TI_RX_ROWS", 256);
+  while (R < 512 && 2 * R <= want_rows) R *= 2;
+  while (R > 64 && static_cast<size_t>(view.words) * R * 4 > kFeatLdsMax) R >>= 1;
+  if (static_cast<size_t>(view.words) * R * 4 > kFeatLdsMax) return false;
+  view.rows = R;
+  view.L = rt.L;
+  view.kary = 0;
+  if (env_int(sizeof(XT) == 4 ? "TI_KARY" : "TI_KARY64", 1) != 0) kary_tables(rt, &view.tbl, &view.kary);
+  else eytzinger_tables(rt, &view.tbl);
+  desc->clear();
+  for (const auto& lv : levels) {
+    for (size_t j = 0; j < lv.size(); ++j) {
+      const int64_t g = lv[lv.size() - 1 - j];   // bit j is the level D - 1 - j
+      const int fe = d->feature[g];
+      const uint32_t off = static_cast<uint32_t>((fe / 2) * R * 4 + (fe % 2) * 2);
+      desc->push_back((rt.rank(fe, d->threshold[g]) << 16) | off |
+                      ((d->flags[g] & TI_NODE_NAN_LEFT) ? ti::kRxNanLeft : 0u));
+    }
+    if (lv.size() & 1) desc->push_back(ti::kObPad);
+  }
+  if (desc->empty()) desc->push_back(ti::kObPad);   // a forest of lone leaves
+  *out = std::move(view);
+  return true;
+}
+
+// The depths (of the forest's deepest tree) at which a recognised forest takes
+// layout 12 without being forced: those where scripts/bench_oblivious.py
+// measured it no slower than the layout chosen otherwise.  None so far: at 1M
+// float32 rows it took 3.52 ms against the binned heap's 1.88 at depth 6, 4.71
+// against 2.82 at depth 8 and 4.16 against layout 9's 2.88 at depth 10, every
+// spread under 0.2 % (profiles/oblivious_bench.jsonl; DESIGN.md 3.9 says what
+// bounds it).
+bool ob_default_depth(int D) {
+  (void)D;
+  return false;
+}
+
+// Plans and packs layout 12, or returns false and leaves the forest untouched.
+bool plan_oblivious(const ti_forest_desc* d, ti_forest* f) {
+  if (f->has_cat || f->linear || f->zero_rule) return false;
+  const int T = d->n_trees, LW = d->leaf_width;
+  const size_t acc_sz = f->accum == TI_F64 ? 8 : 4;
+  std::vector<std::vector<int64_t>> levels(T);
+  std::vector<int64_t> leaf_at;
+  RecArrays rec;
+  std::vector<int64_t> leaf_base(T, 0);
+  std::vector<int32_t> leaf_ids;
+  std::vector<uint32_t> first(T, 0);
+  for (int t = 0; t < T; ++t) {
+    if (!ob_levels(d, t, &levels[t], &leaf_at)) return false;
+    leaf_base[t] = static_cast<int64_t>(leaf_ids.size());
+    for (const int64_t g : leaf_at) leaf_ids.push_back(d->leaf_id[g]);
+    if (t + 1 < T) first[t + 1] = first[t] + static_cast<uint32_t>((levels[t].size() + 1) & ~size_t(1));
+  }
+  if (!pack_ob_view<float>(d, levels, &rec.rx[0], &rec.ob_desc[0]) ||
+      !pack_ob_view<double>(d, levels, &rec.rx[1], &rec.ob_desc[1]) || rec.rx[0].rows != rec.rx[1].rows)
+    return false;
+  const int R = rec.rx[0].rows;
+  const size_t cap = ob_stage_cap(rec.rx[0].words, R);
+  const size_t staged_max = std::min(cap, kObStageMax);
+  // the image: one zero word (an empty stage's clamped load reads the word
+  // before its first), the staged tables in tree order, then the gathered ones
+  auto table_bytes = [&](int t) { return align16((acc_sz * LW) << levels[t].size()); };
+  std::vector<uint32_t> base(T + 1, 0), depth(T, 0), goff(T, 0);
+  uint64_t at = 16;
+  for (int t = 0; t < T; ++t) {
+    base[t] = static_cast<uint32_t>(at);
+    depth[t] = static_cast<uint32_t>(levels[t].size());
+    if (table_bytes(t) <= staged_max) at += table_bytes(t);
+    else depth[t] |= ti::kObGather;
+    if (at >= (uint64_t(1) << 31)) return false;
+  }
+  base[T] = static_cast<uint32_t>(at);
+  bool gathers = false;
+  for (int t = 0; t < T; ++t) {
+    if (!(depth[t] & ti::kObGather)) continue;
+    gathers = true;
+    goff[t] = static_cast<uint32_t>(at >> 4);
+    at += table_bytes(t);
+    if ((at >> 4) >= (uint64_t(1) << 32)) return false;
+  }
+  rec.ob_img.assign(at, 0);
+  for (int t = 0; t < T; ++t) {
+    unsigned char* dst = rec.ob_img.data() + ((depth[t] & ti::kObGather) ? static_cast<size_t>(goff[t]) << 4 : base[t]);
+    ob_levels(d, t, &levels[t], &leaf_at);
+    for (size_t p = 0; p < leaf_at.size(); ++p)
+      for (int k = 0; k < LW; ++k) {
+        const double v = d->leaf_value[leaf_at[p] * LW + k];
+        if (acc_sz == 8) {
+          std::memcpy(dst + (p * LW + k) * 8, &v, 8);
+        } else {
+          const float v32 = static_cast<float>(v);
+          std::memcpy(dst + (p * LW + k) * 4, &v32, 4);
+        }
+      }
+  }
+  // a stage: consecutive trees while their staged bytes fit one buffer
+  rec.lx_stage.assign(1, 0);
+  for (int t0 = 0; t0 < T;) {
+    int t1 = t0 + 1;
+    while (t1 < T && base[t1 + 1] - base[t0] <= cap) ++t1;
+    rec.lx_stage.push_back(t1);
+    t0 = t1;
+  }
+  rec.ob_first = std::move(first);
+  rec.ob_goff = std::move(goff);
+  // nothing can fail any more: the plan becomes the forest's
+  HostImage& h = *f->host;
+  for (int i = 0; i < 2; ++i) f->rx[i] = rec.rx[i];
+  f->n_stages = static_cast<int32_t>(rec.lx_stage.size() - 1);
+  f->lx_stage_cap = static_cast<int64_t>(cap);
+  f->lx_ilp = 1;
+  f->ob_gather = gathers ? 1 : 0;
+  h.rx_base = std::move(base);
+  h.rx_nint = std::move(depth);
+  h.leaf_base = std::move(leaf_base);
+  h.exp_leaf_ids = std::move(leaf_ids);
+  h.rec = std::move(rec);
+  return true;
+}
+
 // The record family's choice becomes the forest's: plan scalars into the
 // forest, arrays into its host image (moved, not copied).
 void commit_records(ti_forest* f, RecSlots&& s, RecCandidate&& c) {
@@ -1591,10 +1785,13 @@ void commit_records(ti_forest* f, RecSlots&& s, RecCandidate&& c) {
 // (1) otherwise and for every LightGBM-rule forest;
 // LightGBM-rule forests deeper than 8 take the categorical records (11) where
 // plan_crecord accepts them;
-// TI_FORCE_LAYOUT=heap|explicit|rexplicit|lexplicit|hexplicit|texplicit|cheap|crecord
+// TI_FORCE_LAYOUT=heap|explicit|rexplicit|lexplicit|hexplicit|texplicit|cheap|crecord|oblivious
 // overrides (tests run every layout on the same forest); cheap puts any
-// categorical forest of depth <= 8 on layout 10, whichever rule it uses, and
-// crecord any categorical forest that plan_crecord accepts on layout 11.
+// categorical forest of depth <= 8 on layout 10, whichever rule it uses,
+// crecord any categorical forest that plan_crecord accepts on layout 11, and
+// oblivious any forest that plan_oblivious recognises (every tree complete to
+// its own depth, one split a level: CatBoost's) on layout 12, which no forest
+// takes by default yet (ob_default_depth).
 int choose_layout(const ti_forest_desc* desc, ti_forest* f) {
   HostImage& h = *f->host;
   const size_t acc_sz = f->accum == TI_F64 ? 8 : 4;
@@ -1604,6 +1801,13 @@ int choose_layout(const ti_forest_desc* desc, ti_forest* f) {
     for (int t = 0; t < f->T; ++t) h.group[t] = desc->tree_group[t];
   const char* force = env_knob("TI_FORCE_LAYOUT");
   const std::string want = force ? force : "";
+  // oblivious forests (every level of a tree one split: CatBoost's) take layout
+  // 12 when forced, and by default at the depths where it measured no slower
+  // than the layout chosen below (ob_default_depth)
+  if ((want == "oblivious" || (want.empty() && ob_default_depth(D))) && plan_oblivious(desc, f)) {
+    f->layout = kLayoutOblivious;
+    return TI_OK;
+  }
   bool use_heap = D <= kMaxHeapDepth;
   if (want == "heap" && D <= kMaxHeapDepth) use_heap = true;
   if (want == "explicit" || want == "rexplicit" || want == "lexplicit" || want == "hexplicit" ||
