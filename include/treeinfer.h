@@ -128,7 +128,7 @@
 extern "C" {
 #endif
 
-#define TI_ABI_VERSION 11
+#define TI_ABI_VERSION 12
 
 /* return codes */
 #define TI_OK               0
@@ -365,6 +365,13 @@ typedef struct ti_forest_info {
   int64_t shap_table_bytes;   /* device bytes of the built table                     */
   double  shap_table_build_ms;/* host wall time of the last table build             */
   int32_t pre_steps;          /* ABI 9: pre-steps S applied where X enters (0: none) */
+  /* ABI 12: the sparse image of ti_predict_csr (device slot 0) */
+  int32_t sparse_cols;        /* U, the distinct columns the forest splits on; -1 until
+                                 the first ti_predict_csr builds the image            */
+  int32_t sparse_walk[2];     /* what a CSR batch of float32 [0] / float64 [1] values
+                                 takes: 0 no image yet, 1 the LDS image of the used
+                                 columns, 2 the per-row search                        */
+  int32_t sparse_rows[2];     /* rows per tile of that walk                           */
 } ti_forest_info;
 
 /* ti_forest_set_option options (ABI 4) */
@@ -449,6 +456,35 @@ int ti_output_shape(const ti_forest* forest, int32_t output_kind, int64_t n_rows
 int ti_predict(ti_forest* forest, const void* X, int32_t x_dtype, int64_t n_rows,
                int32_t n_cols, int64_t row_stride, int32_t output_kind,
                void* out, int64_t out_len);
+
+/* ABI 12: host-buffer predict of rows in CSR form (scipy.sparse.csr_matrix:
+ * indptr [n_rows + 1], non-decreasing, starting at any base b; indices and
+ * values read from element b on; within a row the indices strictly increase
+ * and lie in [0, n_cols); values of x_dtype TI_F32 / TI_F64).  The answer is
+ * bit for bit what ti_predict writes for the dense [n_rows, n_cols] matrix that
+ * holds each stored value as stored (explicit zeros and NaNs included) and, by
+ * `absent`, +0.0 or NaN everywhere else: an absent zero goes through
+ * lgb_zero_map as a dense 0.0 does, and a feature >= n_cols is NaN under either
+ * mode.  The three arrays are checked in the one pass that copies them to
+ * pinned staging (the whole call's arrays), before anything is launched:
+ * TI_ERR_INVALID for a decreasing indptr, an index out of range or a row that
+ * is not strictly increasing.  Rows are sharded over the forest's devices as
+ * ti_predict shards them; on a device they go in blocks of whole 256-row tiles
+ * whose three arrays fit TI_CHUNK_MB.  Serves TI_OUTPUT_MARGIN, TI_OUTPUT_PREDICT
+ * and TI_OUTPUT_LEAF of any forest the float explicit kernel can walk
+ * (numerical splits, both categorical rules, vector leaves, multiclass groups,
+ * either accumulator, lgb_zero_map).  TI_ERR_UNSUPPORTED, the handle serving
+ * on, for every other output kind and for forests with linear leaves, pre-steps,
+ * tree weights or more than 16 output groups (group parts).  The first call
+ * builds the forest's sparse image on every device, which
+ * ti_forest_info.device_bytes then counts.  Thread-safe per handle.
+ * Replaces: XGBoosterPredict on a DMatrix from CSR (absent = NaN),
+ *           LGBM_BoosterPredictForCSR and Forest*.predict(csr) (absent = 0). */
+#define TI_CSR_ABSENT_ZERO 0   /* an entry not stored reads +0.0 (scipy, LightGBM, sklearn) */
+#define TI_CSR_ABSENT_NAN  1   /* an entry not stored is missing (xgboost DMatrix from CSR)   */
+int ti_predict_csr(ti_forest* forest, const int64_t* indptr, const int32_t* indices,
+                   const void* values, int32_t x_dtype, int64_t n_rows, int32_t n_cols,
+                   int32_t absent, int32_t output_kind, void* out, int64_t out_len);
 
 /* Device-resident predict on one of the forest's devices (device_slot indexes
  * the devices passed to ti_forest_create).  X and out are device pointers on

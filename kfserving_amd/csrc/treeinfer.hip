@@ -24,6 +24,7 @@
 #include "treeinfer_approx.h"
 #include "treeinfer_quantile.h"
 #include "treeinfer_pre.h"
+#include "treeinfer_sparse.h"
 
 namespace {
 
@@ -52,6 +53,8 @@ void free_device(DeviceForest& d) {
   free_interv(d);
   free_approx(d);
   free_quantile(d);
+  d.sparse_mem.release();
+  static_cast<SparsePtrs&>(d) = SparsePtrs();
   free_scratch(d);
   if (d.interact_done) (void)hipEventDestroy(d.interact_done);
   if (d.interact_buf) (void)hipFree(d.interact_buf);
@@ -291,21 +294,13 @@ struct LaunchPlan {
 // and output `kind`.  Host arithmetic only: it makes no HIP call, and reads
 // the knobs TI_BHEAP_FIX / TI_BHEAP_NG / TI_BIN_XPF (every call) and TI_HEAP_LDS_KB /
 // TI_BHEAP_STAGE (once).
-int plan_launch(const ti_forest* f, const DeviceForest& d, int xdt, int kind, LaunchPlan* p) {
-  const size_t xs = dtype_size(xdt);
-  const int ii = xdt == TI_F64 ? 1 : 0;
-  const Tile t = tile_for(f, xdt);
-  const int R = t.R;
-  p->R = R;
-  p->block = R;
-  p->lds = t.feat_bytes + 16;   // feature image + NaN flag word
-
+// The part of a plan every walk shares: the key's types and the model's scalars.
+void plan_model(const ti_forest* f, const DeviceForest& d, int xdt, int kind, LaunchPlan* p) {
   ti::KernelKey& key = p->key;
   key = ti::KernelKey{};
   key.x64 = xdt == TI_F64;
   key.acc64 = f->accum == TI_F64;
   key.K = f->K;
-  key.feat_lds = t.feat_lds;
   key.zero_rule = f->zero_rule != 0;
 
   KArgs& a = p->a;
@@ -323,6 +318,20 @@ int plan_launch(const ti_forest* f, const DeviceForest& d, int xdt, int kind, La
   a.average_divisor = f->divisor;
   for (int k = 0; k < ti::kMaxGroups; ++k) a.base[k] = f->base[k];
   a.tree_group = d.tree_group;
+}
+
+int plan_launch(const ti_forest* f, const DeviceForest& d, int xdt, int kind, LaunchPlan* p) {
+  const size_t xs = dtype_size(xdt);
+  const int ii = xdt == TI_F64 ? 1 : 0;
+  const Tile t = tile_for(f, xdt);
+  const int R = t.R;
+  p->R = R;
+  p->block = R;
+  p->lds = t.feat_bytes + 16;   // feature image + NaN flag word
+  plan_model(f, d, xdt, kind, p);
+  ti::KernelKey& key = p->key;
+  key.feat_lds = t.feat_lds;
+  KArgs& a = p->a;
 
   if (heap_fields(f->layout)) {
     // [feature image][flag][stage area = S tree records]
@@ -796,6 +805,282 @@ int predict_shard(ti_forest* f, int slot, DeviceForest& d, const unsigned char* 
   TI_HIP(hipMemcpyAsync(d.ho_pin, d.out_buf, out_bytes, hipMemcpyDeviceToHost, d.stream));
   TI_HIP(hipStreamSynchronize(d.stream));
   copy_parallel(out, d.ho_pin, out_bytes);
+  return TI_OK;
+}
+
+// ------------------------------------------------------------------ CSR rows
+// ti_predict_csr (treeinfer_sparse.h).  A forest keeps a host
+// copy of the descriptor arrays the layout-1 packer reads; the first CSR call
+// packs them, derives the sparse image and uploads it to every replica.
+void keep_sparse_source(const ti_forest_desc* d, ti_forest* f) {
+  if (d->lin_offset) f->sparse_refused = "CSR rows of a forest with linear leaves (a leaf's model reads raw columns)";
+  else if (d->n_pre_steps > 0) f->sparse_refused = "CSR rows of a forest with pre-steps (they transform every element, stored or not)";
+  else if (d->tree_weight) f->sparse_refused = "CSR rows of a forest with tree weights (its quantile kind has no CSR walk)";
+  if (!f->sparse_refused.empty()) return;
+  auto src = std::make_unique<ti_forest::SparseSource>();
+  const int64_t N = d->n_nodes, T = d->n_trees;
+  src->tree_offset.assign(d->tree_offset, d->tree_offset + T + 1);
+  src->feature.assign(d->feature, d->feature + N);
+  src->left.assign(d->left, d->left + N);
+  src->right.assign(d->right, d->right + N);
+  src->leaf_id.assign(d->leaf_id, d->leaf_id + N);
+  src->threshold.assign(d->threshold, d->threshold + N);
+  src->leaf_value.assign(d->leaf_value, d->leaf_value + N * d->leaf_width);
+  src->flags.assign(d->flags, d->flags + N);
+  if (d->cover) src->cover.assign(d->cover, d->cover + N);   // the packer's node order reads it
+  src->desc = *d;
+  src->desc.tree_offset = src->tree_offset.data();
+  src->desc.feature = src->feature.data();
+  src->desc.left = src->left.data();
+  src->desc.right = src->right.data();
+  src->desc.leaf_id = src->leaf_id.data();
+  src->desc.threshold = src->threshold.data();
+  src->desc.leaf_value = src->leaf_value.data();
+  src->desc.flags = src->flags.data();
+  src->desc.cover = d->cover ? src->cover.data() : nullptr;
+  src->desc.tree_group = nullptr;   // every replica holds the groups already
+  src->desc.base_margin = nullptr;
+  if (f->has_cat) {
+    src->cat_bits.assign(d->cat_bits, d->cat_bits + d->n_cat_words);
+    src->cat_offset.assign(d->cat_offset, d->cat_offset + N);
+    src->cat_nwords.assign(d->cat_nwords, d->cat_nwords + N);
+    src->desc.cat_bits = src->cat_bits.data();
+    src->desc.cat_offset = src->cat_offset.data();
+    src->desc.cat_nwords = src->cat_nwords.data();
+  }
+  f->sparse_src = std::move(src);
+}
+
+int ensure_sparse(ti_forest* f) {
+  if (f->sparse_ready.load(std::memory_order_acquire)) return TI_OK;
+  std::lock_guard<std::mutex> lk(f->shap_mu);
+  if (f->sparse_ready.load(std::memory_order_relaxed)) return TI_OK;
+  HostImage h;
+  with_acc(f->accum, [&](auto acc) {
+    pack_explicit<decltype(acc)>(&f->sparse_src->desc, &h);
+    return true;
+  });
+  // a layout-1 forest with an internal node walks its resident arrays; every
+  // other forest gets the packed set of its own.  A forest of leaves alone
+  // gets one node nobody follows, so that every clamped node load has a target.
+  const bool share = f->layout == kLayoutExplicit && !h.nodes.empty();
+  if (h.nodes.empty()) {
+    h.nodes.push_back(ExpNode{0.0f, 0u, ~0, ~0});
+    h.thr64.push_back(0.0);
+  }
+  std::vector<int32_t> slot_of_col(f->F, -1), cols;
+  for (const ExpNode& e : h.nodes)
+    if (static_cast<int32_t>(e.meta & ti::kMetaFeatMask) < f->F) slot_of_col[e.meta & ti::kMetaFeatMask] = 0;
+  for (int32_t c = 0; c < f->F; ++c)
+    if (slot_of_col[c] == 0) {
+      slot_of_col[c] = static_cast<int32_t>(cols.size());
+      cols.push_back(c);
+    }
+  std::vector<ExpNode> slot_nodes(h.nodes);
+  for (ExpNode& e : slot_nodes)
+    e.meta = (e.meta & ~ti::kMetaFeatMask) |
+             (cols.empty() ? 0u : static_cast<uint32_t>(slot_of_col[e.meta & ti::kMetaFeatMask]));
+  int dev0 = 0;
+  TI_HIP(hipGetDevice(&dev0));
+  int rc = TI_OK;
+  std::vector<int64_t> bytes0;
+  for (auto& dp : f->devs) bytes0.push_back(dp->bytes);
+  for (auto& dp : f->devs) {
+    DeviceForest& d = *dp;
+    if ((rc = fail_hip(hipSetDevice(d.device), "hipSetDevice"))) break;
+    auto up = [&](auto** dst, const auto& src) {
+      if (rc == TI_OK) rc = upload(&d.sparse_mem, dst, src, &d.bytes);
+    };
+    up(&d.sp_slot_nodes, slot_nodes);
+    up(&d.sp_cols, cols);
+    up(&d.sp_slot_of_col, slot_of_col);
+    if (share) {
+      d.sp_ex = {d.nodes, d.thr64, d.node_base, d.root, d.leaf_base, d.leaves, d.exp_leaf_ids, d.cat_words};
+    } else {
+      up(&d.sp_ex.nodes, h.nodes);
+      up(&d.sp_ex.thr64, h.thr64);
+      up(&d.sp_ex.node_base, h.node_base);
+      up(&d.sp_ex.root, h.root);
+      up(&d.sp_ex.leaf_base, h.leaf_base);
+      up(&d.sp_ex.leaves, h.leaves);
+      up(&d.sp_ex.exp_leaf_ids, h.exp_leaf_ids);
+      up(&d.sp_ex.cat_words, h.cat_words);
+    }
+    if (rc) break;
+  }
+  if (rc) {   // nothing half-built survives; the source stays for the next call
+    const std::string err = g_last_error;
+    for (size_t i = 0; i < f->devs.size(); ++i) {
+      (void)hipSetDevice(f->devs[i]->device);
+      f->devs[i]->sparse_mem.release();
+      static_cast<SparsePtrs&>(*f->devs[i]) = SparsePtrs();
+      f->devs[i]->bytes = bytes0[i];
+    }
+    (void)hipGetLastError();
+    (void)hipSetDevice(dev0);
+    return fail(rc, err);
+  }
+  TI_HIP(hipSetDevice(dev0));
+  f->sparse_U = static_cast<int32_t>(cols.size());
+  f->sparse_node_last = static_cast<int64_t>(h.nodes.size()) - 1;
+  f->sparse_src.reset();
+  f->sparse_ready.store(true, std::memory_order_release);
+  return TI_OK;
+}
+
+// The regime and the tile of CSR batches of input type xdt, beside the other
+// layouts' choices: the LDS image of the U used columns at the largest R of
+// 256 / 128 / 64 whose [U][R] image fits the feature budget (kFeatLdsMax, as
+// layout 1's dense image); the per-row search when none does, and under
+// TI_SPARSE_SEARCH=1 (a developer knob, read every call).
+struct SparseTile {
+  bool search;
+  int R;
+};
+
+SparseTile sparse_tile_for(const ti_forest* f, int xdt) {
+  const int R = pick_rows(std::max(f->sparse_U, 1), dtype_size(xdt), 0);
+  if (R == 0 || env_int("TI_SPARSE_SEARCH", 0) != 0) return {true, 256};
+  return {false, R};
+}
+
+int plan_sparse(const ti_forest* f, const DeviceForest& d, int xdt, int kind, int absent, LaunchPlan* p) {
+  const SparseTile t = sparse_tile_for(f, xdt);
+  plan_model(f, d, xdt, kind, p);
+  p->R = p->block = t.R;
+  p->lds = t.search ? 16 : ti::sparse_lds_bytes(std::max(f->sparse_U, 1), t.R, dtype_size(xdt));
+  p->key.walk = t.search ? ti::Walk::SparseSearch : ti::Walk::SparseImage;
+  KArgs& a = p->a;
+  a.nodes = t.search ? d.sp_ex.nodes : d.sp_slot_nodes;
+  a.thr64 = d.sp_ex.thr64;
+  a.node_base = d.sp_ex.node_base;
+  a.root = d.sp_ex.root;
+  a.leaf_base = d.sp_ex.leaf_base;
+  a.leaves = d.sp_ex.leaves;
+  a.exp_leaf_ids = d.sp_ex.exp_leaf_ids;
+  a.cat_words = d.sp_ex.cat_words;
+  a.sp_slot_of_col = d.sp_slot_of_col;
+  a.sp_cols = d.sp_cols;
+  a.sp_U = f->sparse_U;
+  a.sp_absent_nan = absent == TI_CSR_ABSENT_NAN;
+  a.sp_node_last = f->sparse_node_last;
+  return TI_OK;
+}
+
+// One device's rows [r0, r1) of a CSR call.  stage() cuts them into blocks of
+// whole 256-row tiles whose three arrays fit TI_CHUNK_MB (one tile at least)
+// and copies them into the replica's pinned staging, block after block, each
+// as [indptr from 0][indices][values], checking every entry on the way; run()
+// then sends the blocks through one device scratch buffer on the replica's
+// stream (H2D, kernel, D2H behind each other) and copies the result out.
+struct CsrShard {
+  struct Block {
+    int64_t row, rows, nnz;
+    size_t at, bytes;   // in the staging buffer; offsets of indices / values inside it below
+    size_t idx_at, val_at;
+  };
+  std::vector<Block> blocks;
+  size_t block_max = 0;
+};
+
+int stage_csr(DeviceForest& d, const int64_t* indptr, const int32_t* indices, const unsigned char* values,
+              int xdt, int64_t r0, int64_t r1, int32_t cols, CsrShard* sh) {
+  const size_t xs = dtype_size(xdt);
+  const size_t cap = static_cast<size_t>(std::max(env_int("TI_CHUNK_MB", 64), 1)) << 20;
+  size_t total = 0;
+  for (int64_t r = r0; r < r1;) {
+    CsrShard::Block b;
+    b.row = r;
+    int64_t e = r;
+    size_t bytes = 0;
+    do {   // whole tiles while they fit, one at least
+      const int64_t n = std::min<int64_t>(e + 256, r1);
+      for (int64_t j = e; j < n; ++j)
+        if (indptr[j + 1] < indptr[j])
+          return fail(TI_ERR_INVALID, "indptr decreases at row " + std::to_string(j));
+      const size_t nnz = static_cast<size_t>(indptr[n] - indptr[r]);
+      bytes = align16(static_cast<size_t>(n - r + 1) * 8) + align16(nnz * 4) + align16(nnz * xs);
+      if (e > r && bytes > cap) break;
+      e = n;
+    } while (e < r1);
+    b.rows = e - r;
+    b.nnz = indptr[e] - indptr[r];
+    if (b.nnz > 0xffffffffll)
+      return fail(TI_ERR_UNSUPPORTED, "more than 2^32 stored entries in one tile of 256 rows");
+    b.idx_at = align16(static_cast<size_t>(b.rows + 1) * 8);
+    b.val_at = b.idx_at + align16(static_cast<size_t>(b.nnz) * 4);
+    b.bytes = b.val_at + align16(static_cast<size_t>(b.nnz) * xs);
+    b.at = total;
+    total += b.bytes;
+    sh->block_max = std::max(sh->block_max, b.bytes);
+    sh->blocks.push_back(b);
+    r = e;
+  }
+  TI_HIP(hipSetDevice(d.device));
+  int rc = grow(&d.hx_pin, &d.hx_cap, total, true);
+  if (rc) return rc;
+  for (const CsrShard::Block& b : sh->blocks) {
+    unsigned char* base = static_cast<unsigned char*>(d.hx_pin) + b.at;
+    int64_t* ip = reinterpret_cast<int64_t*>(base);
+    int32_t* ix = reinterpret_cast<int32_t*>(base + b.idx_at);
+    const int64_t e0 = indptr[b.row];
+    for (int64_t j = 0; j <= b.rows; ++j) ip[j] = indptr[b.row + j] - e0;
+    for (int64_t j = 0; j < b.rows; ++j) {
+      int64_t prev = -1;
+      for (int64_t e = indptr[b.row + j]; e < indptr[b.row + j + 1]; ++e) {
+        const int32_t c = indices[e];
+        if (c < 0 || c >= cols)
+          return fail(TI_ERR_INVALID, "column index " + std::to_string(c) + " of row " +
+                                          std::to_string(b.row + j) + " is outside [0, n_cols)");
+        if (c <= prev)
+          return fail(TI_ERR_INVALID, "the column indices of row " + std::to_string(b.row + j) +
+                                          " are not strictly increasing");
+        prev = c;
+        ix[e - e0] = c;
+      }
+    }
+    std::memcpy(base + b.val_at, values + static_cast<size_t>(e0) * xs, static_cast<size_t>(b.nnz) * xs);
+  }
+  return TI_OK;
+}
+
+int run_csr(ti_forest* f, DeviceForest& d, const CsrShard& sh, int xdt, int64_t r0, int32_t cols,
+            int absent, int kind, unsigned char* out) {
+  TI_HIP(hipSetDevice(d.device));
+  const size_t os = dtype_size(output_dtype(f, kind)) * output_width(f, kind);
+  LaunchPlan p;
+  int rc = plan_sparse(f, d, xdt, kind, absent, &p);
+  if (rc) return rc;
+  KernelFn fn = ti::select(p.key);
+  if ((rc = ensure_lds_attr(d.device, fn))) return rc;
+  occ_note(fn, p.block, p.lds);
+  int64_t rows = 0, rows_max = 0;
+  for (const auto& b : sh.blocks) {
+    rows += b.rows;
+    rows_max = std::max(rows_max, b.rows);
+  }
+  if ((rc = grow(&d.ho_pin, &d.ho_cap, static_cast<size_t>(rows) * os, true))) return rc;
+  ScratchHold in_buf(d, d.stream), out_buf(d, d.stream);   // given back behind the last block
+  if (!in_buf.take(sh.block_max) || !out_buf.take(static_cast<size_t>(rows_max) * os))
+    return fail(TI_ERR_NOMEM, "CSR block scratch allocation failed");
+  unsigned char* din = static_cast<unsigned char*>(in_buf.p);
+  for (const auto& b : sh.blocks) {
+    TI_HIP(hipMemcpyAsync(din, static_cast<unsigned char*>(d.hx_pin) + b.at, b.bytes,
+                          hipMemcpyHostToDevice, d.stream));
+    p.a.sp_indptr = reinterpret_cast<const int64_t*>(din);
+    p.a.sp_indices = reinterpret_cast<const int32_t*>(din + b.idx_at);
+    p.a.sp_values = din + b.val_at;
+    p.a.n_rows = b.rows;
+    p.a.n_cols = cols;
+    p.a.out = out_buf.p;
+    hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>((b.rows + p.R - 1) / p.R)), dim3(p.block), p.lds,
+                       d.stream, p.a);
+    TI_HIP(hipGetLastError());
+    TI_HIP(hipMemcpyAsync(static_cast<unsigned char*>(d.ho_pin) + static_cast<size_t>(b.row - r0) * os,
+                          out_buf.p, static_cast<size_t>(b.rows) * os, hipMemcpyDeviceToHost, d.stream));
+  }
+  TI_HIP(hipStreamSynchronize(d.stream));
+  copy_parallel(out, d.ho_pin, static_cast<size_t>(rows) * os);
   return TI_OK;
 }
 
@@ -1277,6 +1562,9 @@ int create_chunked(const ti_forest_desc* d, const std::vector<int>& depth, const
   fill_model(d, depth, f.get());
   f->lgb_zero_map = 0;   // the parts hold it: a parent launches no tree kernel
   keep_quantile_source(d, f.get());   // more than 16 groups: the refusal alone
+  // the part loop hands each part dense device rows; it has no CSR form
+  f->sparse_refused = "CSR rows of a forest served in group parts (more than " +
+                      std::to_string(ti::kMaxGroups) + " output groups)";
   const int K = d->n_groups, LW = d->leaf_width;
   for (int k0 = 0; k0 < K; k0 += ti::kMaxGroups) {
     const int kc = std::min(ti::kMaxGroups, K - k0);
@@ -1400,6 +1688,7 @@ int ti_forest_create(const ti_forest_desc* desc, const int32_t* devices, int32_t
   keep_shap_source(desc, f.get());
   keep_approx_source(desc, f.get());
   keep_quantile_source(desc, f.get());
+  keep_sparse_source(desc, f.get());
   if (desc->n_pre_steps > 0) {
     f->host->pre_op.assign(desc->pre_op, desc->pre_op + desc->n_pre_steps);
     f->host->pre_const.assign(desc->pre_const,
@@ -1517,6 +1806,13 @@ int ti_forest_get_info(const ti_forest* f, ti_forest_info* info) {
   info->shap_table_bytes = info->shap_table == 1 ? sf->shap_tab_len * sf->shap_tab_mt : 0;
   info->shap_table_build_ms = sf->shap_tab_build_ms;
   info->pre_steps = f->pre_steps;
+  const bool sp = f->sparse_ready.load(std::memory_order_acquire);
+  info->sparse_cols = sp ? f->sparse_U : -1;
+  for (int i = 0; i < 2; ++i) {
+    const SparseTile t = sparse_tile_for(f, i ? TI_F64 : TI_F32);
+    info->sparse_walk[i] = !sp ? 0 : t.search ? 2 : 1;
+    info->sparse_rows[i] = sp ? t.R : 0;
+  }
   return TI_OK;
 }
 
@@ -1622,6 +1918,74 @@ int ti_predict(ti_forest* f, const void* X, int32_t xdt, int64_t rows, int32_t c
   for (int i = 0; i < nd; ++i)
     if (rcs[i]) return fail(rcs[i], "device slot " + std::to_string(i) + ": " + errs[i]);
   return TI_OK;
+}
+
+int ti_predict_csr(ti_forest* f, const int64_t* indptr, const int32_t* indices, const void* values,
+                   int32_t xdt, int64_t rows, int32_t cols, int32_t absent, int32_t kind, void* out,
+                   int64_t out_len) {
+  if (!f) return fail(TI_ERR_INVALID, "null forest");
+  if (xdt != TI_F32 && xdt != TI_F64) return fail(TI_ERR_INVALID, "x_dtype must be TI_F32 or TI_F64");
+  if (absent != TI_CSR_ABSENT_ZERO && absent != TI_CSR_ABSENT_NAN)
+    return fail(TI_ERR_INVALID, "absent must be TI_CSR_ABSENT_ZERO or TI_CSR_ABSENT_NAN");
+  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_TREE_QUANTILE) return fail(TI_ERR_INVALID, "bad output kind");
+  if (kind != TI_OUTPUT_MARGIN && kind != TI_OUTPUT_PREDICT && kind != TI_OUTPUT_LEAF)
+    return fail(TI_ERR_UNSUPPORTED, "CSR rows serve TI_OUTPUT_MARGIN, TI_OUTPUT_PREDICT and "
+                                    "TI_OUTPUT_LEAF; output kind " + std::to_string(kind) +
+                                    " needs dense rows (ti_predict)");
+  if (!f->sparse_refused.empty()) return fail(TI_ERR_UNSUPPORTED, f->sparse_refused);
+  if (rows < 0) return fail(TI_ERR_INVALID, "negative n_rows");
+  if (rows == 0) return TI_OK;
+  if (!indptr || !out) return fail(TI_ERR_INVALID, "null data pointer");
+  if (cols <= 0) return fail(TI_ERR_INVALID, "n_cols must be > 0");
+  if (indptr[0] < 0) return fail(TI_ERR_INVALID, "indptr starts below 0");
+  if (out_len < rows * output_width(f, kind))
+    return fail(TI_ERR_INVALID, "output buffer too small: need " +
+                                    std::to_string(rows * output_width(f, kind)) + " elements");
+  // the end of indptr is trusted only once the staging pass has seen every step
+  int rc = ensure_sparse(f);
+  if (rc) return rc;
+  const int nd = static_cast<int>(f->devs.size());
+  const size_t os = dtype_size(output_dtype(f, kind)) * output_width(f, kind);
+  const int64_t per = (rows + nd - 1) / nd;
+  const unsigned char* vb = static_cast<const unsigned char*>(values);
+  unsigned char* ob = static_cast<unsigned char*>(out);
+  // every shard is staged and checked before any is launched; a replica's
+  // staging is its own for the whole call
+  std::vector<std::unique_lock<std::mutex>> locks;
+  std::vector<CsrShard> shards(nd);
+  for (int i = 0; i < nd && per * i < rows; ++i) locks.emplace_back(f->devs[i]->mu);
+  const int ns = static_cast<int>(locks.size());
+  if (!indices || !values) {   // legal only for a batch that stores nothing
+    for (int64_t r = 0; r < rows; ++r)
+      if (indptr[r + 1] != indptr[0]) return fail(TI_ERR_INVALID, "null data pointer");
+  }
+  auto each_shard = [&](auto work) -> int {
+    std::vector<int> rcs(ns, TI_OK);
+    std::vector<std::string> errs(ns);
+    if (ns == 1) {
+      rcs[0] = work(0, int64_t(0), rows);
+      errs[0] = g_last_error;
+    } else {
+      std::vector<std::thread> th;
+      for (int i = 0; i < ns; ++i)
+        th.emplace_back([&, i]() {
+          rcs[i] = work(i, per * i, std::min(rows, per * (i + 1)));
+          if (rcs[i]) errs[i] = g_last_error;
+        });
+      for (auto& t : th) t.join();
+    }
+    for (int i = 0; i < ns; ++i)
+      if (rcs[i]) return fail(rcs[i], ns == 1 ? errs[i] : "device slot " + std::to_string(i) + ": " + errs[i]);
+    return TI_OK;
+  };
+  rc = each_shard([&](int i, int64_t r0, int64_t r1) {
+    return stage_csr(*f->devs[i], indptr, indices, vb, xdt, r0, r1, cols, &shards[i]);
+  });
+  if (rc) return rc;
+  return each_shard([&](int i, int64_t r0, int64_t r1) {
+    (void)r1;
+    return run_csr(f, *f->devs[i], shards[i], xdt, r0, cols, absent, kind, ob + r0 * os);
+  });
 }
 
 int ti_transform_device(ti_forest* f, int32_t slot, const void* margin, int64_t rows, void* out,

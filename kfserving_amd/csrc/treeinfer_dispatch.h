@@ -1,8 +1,9 @@
 // treeinfer_dispatch.h — kernel selection across the translation units.  Each
 // treeinfer_k_<x><a>.hip instantiates every kernel of one (input type,
 // accumulator type) pair, treeinfer_k_cat.hip the categorical heap's,
-// treeinfer_k_crec.hip the categorical records' and treeinfer_k_obliv.hip the
-// oblivious trees' for all four pairs, so the seven compile in parallel.
+// treeinfer_k_crec.hip the categorical records', treeinfer_k_obliv.hip the
+// oblivious trees' and treeinfer_k_sparse.hip the CSR walk's for all four pairs,
+// so the eight compile in parallel.
 //
 // The host names what it launches with a KernelKey; ti::select(key) is the one
 // way from a key to a kernel.  Each rule that turns a runtime value into a
@@ -38,6 +39,8 @@ enum class Walk {
   CatRecordLgb,     // 11: categorical records, LightGBM's rule  (treeinfer_crec.h)
   Oblivious,        // 12: oblivious trees, every table staged   oblivious_predict_kernel
   ObliviousGather,  // 12: ... some tables gathered              (treeinfer_obliv.h)
+  SparseImage,      // CSR rows, the used columns in an LDS image  sparse_explicit_predict_kernel
+  SparseSearch,     // CSR rows, each column searched in its row   (treeinfer_sparse.h)
 };
 
 struct KernelKey {
@@ -143,6 +146,9 @@ KernelFn select_walk(const KernelKey& k) {
     case Walk::Oblivious:
     case Walk::ObliviousGather:
       break;   // kernels_obliv
+    case Walk::SparseImage:
+    case Walk::SparseSearch:
+      break;   // kernels_sparse
   }
   return nullptr;
 }
@@ -161,11 +167,13 @@ KernelFn kernels_df(const KernelKey& k);    // double X, float acc
 KernelFn kernels_cat(const KernelKey& k);   // the categorical heap, every pair
 KernelFn kernels_crec(const KernelKey& k);  // the categorical records, every pair
 KernelFn kernels_obliv(const KernelKey& k); // the oblivious trees, every pair
+KernelFn kernels_sparse(const KernelKey& k);// the CSR walk, every pair
 
 inline KernelFn select(const KernelKey& k) {
   if (k.walk == Walk::CatHeapXgb || k.walk == Walk::CatHeapLgb) return kernels_cat(k);
   if (k.walk == Walk::CatRecordXgb || k.walk == Walk::CatRecordLgb) return kernels_crec(k);
   if (k.walk == Walk::Oblivious || k.walk == Walk::ObliviousGather) return kernels_obliv(k);
+  if (k.walk == Walk::SparseImage || k.walk == Walk::SparseSearch) return kernels_sparse(k);
   if (!k.x64) return k.acc64 ? kernels_fd(k) : kernels_ff(k);
   return k.acc64 ? kernels_dd(k) : kernels_df(k);
 }

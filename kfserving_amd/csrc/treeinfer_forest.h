@@ -311,6 +311,26 @@ struct QuantilePtrs {
   double* quant_weights = nullptr;      // [T]
 };
 
+// The sparse image of ti_predict_csr (treeinfer_sparse.h: ensure_sparse).  The
+// slot nodes, the used columns and slot_of_col are the image's own; ex is the
+// layout-1 set both regimes walk beside them: a layout-1 forest's resident
+// arrays (not owned), or uploads of the image's own for every other layout.
+struct SparsePtrs {
+  ExpNode* sp_slot_nodes = nullptr;    // layout-1 nodes with the slot in the feature field
+  int32_t* sp_cols = nullptr;          // [U] sorted
+  int32_t* sp_slot_of_col = nullptr;   // [F]
+  struct Explicit {
+    ExpNode* nodes = nullptr;
+    double* thr64 = nullptr;
+    int64_t* node_base = nullptr;
+    int32_t* root = nullptr;
+    int64_t* leaf_base = nullptr;
+    void* leaves = nullptr;
+    int32_t* exp_leaf_ids = nullptr;
+    uint32_t* cat_words = nullptr;
+  } sp_ex;
+};
+
 // ti_predict scratch: device buffers + pinned host staging (grown x2)
 struct ScratchBufs {
   void* x_buf = nullptr;
@@ -363,10 +383,10 @@ struct CallScratch {
 // tables (and the tree-quantile tables beside them), freed from the record of
 // what their uploads allocated (forest_mem / shap_mem / approx_mem / quant_mem), and the scratch buffers, which grow() reallocates and
 // free_scratch frees.
-struct DeviceForest : ForestPtrs, ShapPtrs, ApproxPtrs, QuantilePtrs, ScratchBufs {
+struct DeviceForest : ForestPtrs, ShapPtrs, ApproxPtrs, QuantilePtrs, SparsePtrs, ScratchBufs {
   int device = -1;
   hipStream_t stream = nullptr;
-  DeviceAllocs forest_mem, shap_mem, approx_mem, quant_mem;
+  DeviceAllocs forest_mem, shap_mem, approx_mem, quant_mem, sparse_mem;
   std::atomic<int32_t> shap_tab_state{0};   // 0 not tried, 1 built, -1 failed or over the cap:
                                      // contributions use the extend / unwind kernel
   // TI_OUTPUT_INTERACT scratch (launch_interact: contributions + partials of
@@ -677,5 +697,23 @@ struct ti_forest {
   // background set by ti_forest_set_background, 0 for none.  Written with no
   // call in flight, so calls read it without a lock.
   int64_t interv_B = 0;
+  // CSR rows (ti_predict_csr, treeinfer_sparse.h): sparse_refused names why the
+  // forest cannot serve them (empty: it can).  The sparse image is packed and
+  // uploaded to every replica on the first CSR call (ensure_sparse, under
+  // shap_mu) from this host copy of the descriptor's arrays, which goes once
+  // the replicas hold it.  sparse_U: the distinct columns the forest splits on.
+  std::string sparse_refused;
+  std::atomic<bool> sparse_ready{false};
+  int32_t sparse_U = 0;
+  int64_t sparse_node_last = 0;   // last index of the (padded) node arrays
+  struct SparseSource {
+    ti_forest_desc desc;
+    std::vector<int64_t> tree_offset, cat_offset;
+    std::vector<int32_t> feature, left, right, leaf_id, cat_nwords;
+    std::vector<double> threshold, leaf_value, cover;
+    std::vector<uint8_t> flags;
+    std::vector<uint32_t> cat_bits;
+  };
+  std::unique_ptr<SparseSource> sparse_src;
   std::vector<std::unique_ptr<DeviceForest>> devs;
 };

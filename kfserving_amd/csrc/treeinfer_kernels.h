@@ -136,6 +136,16 @@ struct KArgs {
   const uint32_t* ob_desc;        // level descriptors, a tree's least significant level first
   const uint32_t* ob_first;       // [T] first descriptor of each tree
   const uint32_t* ob_goff;        // [T] 16-byte word of a gathered tree's table in `trees`
+  // CSR rows (treeinfer_sparse.h), after them for the same reason.  `nodes` is
+  // then the sparse image's slot nodes (regime A) or the nodes that hold columns.
+  const int64_t* sp_indptr;       // [n_rows + 1] first entry of each row, from 0
+  const int32_t* sp_indices;      // [nnz] column of each entry, increasing within a row
+  const void* sp_values;          // [nnz] XT
+  const int32_t* sp_slot_of_col;  // [F] slot of a column in the LDS image, -1: never read
+  const int32_t* sp_cols;         // [sp_U] the columns the forest reads, sorted
+  int32_t sp_U;
+  int32_t sp_absent_nan;          // an entry not stored reads NaN (else +0.0)
+  int64_t sp_node_last;           // last valid index of `nodes` / `thr64`
 };
 
 __device__ __forceinline__ size_t align16(size_t x) { return (x + 15) & ~size_t(15); }

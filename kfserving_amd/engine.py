@@ -21,7 +21,7 @@ import numpy as np
 from .forest import (Forest, OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_CONTRIB_INTERV, OUT_INTERACT,
                      OUT_LEAF, OUT_MARGIN, OUT_PREDICT, OUT_TREE_QUANTILE, TI_F32, TI_F64, TI_I32)
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 _LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("TREEINFER_LIB", os.path.join(_LIB_DIR, "libtreeinfer.so"))
 
@@ -29,8 +29,11 @@ EXPORTED_SYMBOLS = (
     "ti_forest_create", "ti_forest_destroy", "ti_forest_get_info", "ti_output_shape",
     "ti_predict", "ti_predict_device", "ti_transform_device", "ti_last_error", "ti_device_count",
     "ti_abi_version", "ti_forest_set_option", "ti_pretransform_device",
-    "ti_forest_set_background", "ti_forest_set_quantiles",
+    "ti_forest_set_background", "ti_forest_set_quantiles", "ti_predict_csr",
 )
+
+# ti_predict_csr: what an entry the matrix does not store reads as
+CSR_ABSENT = {"zero": 0, "nan": 1}
 
 # ti_forest_set_option options (include/treeinfer.h)
 OPT_SHAP_TABLE_ROWS = 1
@@ -111,6 +114,9 @@ class _ForestInfo(ctypes.Structure):
         ("shap_table_bytes", ctypes.c_int64),
         ("shap_table_build_ms", ctypes.c_double),
         ("pre_steps", ctypes.c_int32),
+        ("sparse_cols", ctypes.c_int32),
+        ("sparse_walk", ctypes.c_int32 * 2),
+        ("sparse_rows", ctypes.c_int32 * 2),
     ]
 
 
@@ -147,6 +153,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.ti_output_shape.argtypes = [vp, i32, i64, ctypes.POINTER(i64), ctypes.POINTER(i32)]
         lib.ti_predict.restype = ctypes.c_int
         lib.ti_predict.argtypes = [vp, vp, i32, i64, i32, i64, i32, vp, i64]
+        lib.ti_predict_csr.restype = ctypes.c_int
+        lib.ti_predict_csr.argtypes = [vp, vp, vp, vp, i32, i64, i32, i32, i32, vp, i64]
         lib.ti_predict_device.restype = ctypes.c_int
         lib.ti_predict_device.argtypes = [vp, i32, vp, i32, i64, i32, i64, i32, vp, i64, vp]
         lib.ti_forest_set_option.restype = ctypes.c_int
@@ -275,7 +283,8 @@ class DeviceForest:
     def info(self) -> dict:
         inf = _ForestInfo()
         _check(self._lib, self._lib.ti_forest_get_info(self._handle, ctypes.byref(inf)))
-        return {k: getattr(inf, k) for k, _ in _ForestInfo._fields_}
+        return {k: (list(v) if isinstance(v, ctypes.Array) else v)
+                for k, v in ((k, getattr(inf, k)) for k, _ in _ForestInfo._fields_)}
 
     def set_option(self, option: int, value: int) -> None:
         """ti_forest_set_option: speed knobs that never change results
@@ -330,7 +339,16 @@ class DeviceForest:
     def prepare_input(self, X) -> np.ndarray:
         return prepare_input(self.forest, X)
 
-    def predict(self, X, kind: int = OUT_PREDICT) -> np.ndarray:
+    def predict(self, X, kind: int = OUT_PREDICT, absent: str = "zero") -> np.ndarray:
+        """Dense rows, or any ``scipy.sparse`` matrix, which goes to
+        ti_predict_csr as CSR without being densified.  ``absent`` says what an
+        entry the sparse matrix does not store reads as: ``"zero"`` (scipy,
+        LightGBM, sklearn) or ``"nan"`` (missing: an xgboost DMatrix built
+        from CSR); dense input ignores it."""
+        if absent not in CSR_ABSENT:
+            raise ValueError(f"absent must be 'zero' or 'nan', got {absent!r}")
+        if hasattr(X, "tocsr"):
+            return self._predict_csr(X, kind, CSR_ABSENT[absent])
         X = self.prepare_input(X)
         rows, cols = X.shape
         width = len(self.quantiles) if kind == OUT_TREE_QUANTILE else self.forest.output_width(kind)
@@ -339,6 +357,31 @@ class DeviceForest:
         if rows:
             _check(self._lib, self._lib.ti_predict(self._handle, _ptr(X), xdt, rows, cols, cols,
                                                    kind, _ptr(out), out.shape[0]))
+        if width == 1 and kind != OUT_LEAF:
+            return out
+        return out.reshape(rows, width)
+
+    def _predict_csr(self, X, kind: int, absent: int) -> np.ndarray:
+        """float32 values stay float32, anything else becomes float64, whatever
+        the forest's input type: the values are compared as ti_predict compares
+        dense rows of that type (an XGBoost or sklearn forest casts dense
+        float64 rows to float32 first; cast the matrix to match that)."""
+        csr = X.tocsr()
+        if not csr.has_canonical_format:      # duplicates summed, indices sorted, on a copy
+            csr = csr.copy()
+            csr.sum_duplicates()
+        rows, cols = csr.shape
+        indptr = np.ascontiguousarray(csr.indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(csr.indices, dtype=np.int32)
+        data = np.ascontiguousarray(csr.data, dtype=np.float32 if csr.data.dtype == np.float32
+                                    else np.float64)
+        width = self.forest.output_width(kind)
+        out = np.empty(rows * width, dtype=self.forest.output_dtype(kind))
+        if rows:
+            _check(self._lib, self._lib.ti_predict_csr(
+                self._handle, _ptr(indptr), _ptr(indices), _ptr(data),
+                TI_F32 if data.dtype == np.float32 else TI_F64, rows, cols, absent, kind,
+                _ptr(out), out.shape[0]))
         if width == 1 and kind != OUT_LEAF:
             return out
         return out.reshape(rows, width)
