@@ -118,6 +118,14 @@
  *      (p = 0 when no position qualifies, as numpy's argmax of the mask gives).
  *   The levels are ti_forest_set_quantiles', {0.5} by default: the weighted
  *   median.  The answer is an element of v, bit for bit.
+ *
+ * Small batches (ABI 13; TI_OPT_SMALL_BATCH_ROWS): a request of a few rows may
+ * be walked tree-parallel instead of row-parallel.  The rules above are
+ * unchanged: each output receives its leaf values in tree order, one add a
+ * tree in the accumulator type, so margins, predictions and leaf ids are the
+ * bits of the forest's own walk.  Forests with linear leaves, pre-steps or more
+ * than 16 output groups, every other output kind and CSR rows keep their path
+ * (ti_forest_info.small_walk).
  */
 #ifndef TREEINFER_H_
 #define TREEINFER_H_
@@ -128,7 +136,7 @@
 extern "C" {
 #endif
 
-#define TI_ABI_VERSION 12
+#define TI_ABI_VERSION 13
 
 /* return codes */
 #define TI_OK               0
@@ -372,6 +380,11 @@ typedef struct ti_forest_info {
                                  takes: 0 no image yet, 1 the LDS image of the used
                                  columns, 2 the per-row search                        */
   int32_t sparse_rows[2];     /* rows per tile of that walk                           */
+  int32_t small_walk;         /* ABI 13, TI_OPT_SMALL_BATCH_ROWS: 0 no small batch yet,
+                                 1 the layout-1 node set is resident and the
+                                 tree-parallel walk has served a call, -1 the forest
+                                 keeps its own path at every size (linear leaves,
+                                 pre-steps, more than 16 output groups)               */
 } ti_forest_info;
 
 /* ti_forest_set_option options (ABI 4) */
@@ -395,6 +408,16 @@ typedef struct ti_forest_info {
                                      scratch one pass over a row block may take
                                      (DESIGN.md 3.5); a block is at least one tile
                                      of rows (0: exactly one).  Default 1024.       */
+#define TI_OPT_SMALL_BATCH_ROWS 5 /* ABI 13: a launch of 1 .. this many rows (a device
+                                     shard of ti_predict, a ti_predict_device call)
+                                     of TI_OUTPUT_MARGIN / PREDICT / LEAF takes the
+                                     tree-parallel walk, a workgroup a row and a lane
+                                     a tree: the same bits, for
+                                     requests of a few rows.  0: never.  Default 0 or
+                                     $TI_SMALL_BATCH_ROWS (read at ti_forest_create);
+                                     read every call.  Its first use uploads the
+                                     layout-1 node set of a forest on another layout
+                                     (device_bytes grows; shared with ti_predict_csr). */
 
 /* Upload the forest to each listed device (HIP device ordinals).  HIP is
  * initialised here, not at library load, so a process may fork before it.

@@ -25,6 +25,7 @@
 #include "treeinfer_quantile.h"
 #include "treeinfer_pre.h"
 #include "treeinfer_sparse.h"
+#include "treeinfer_small.h"
 
 namespace {
 
@@ -54,6 +55,7 @@ void free_device(DeviceForest& d) {
   free_approx(d);
   free_quantile(d);
   d.sparse_mem.release();
+  d.ex_mem.release();
   static_cast<SparsePtrs&>(d) = SparsePtrs();
   free_scratch(d);
   if (d.interact_done) (void)hipEventDestroy(d.interact_done);
@@ -811,12 +813,15 @@ int predict_shard(ti_forest* f, int slot, DeviceForest& d, const unsigned char* 
 // ------------------------------------------------------------------ CSR rows
 // ti_predict_csr (treeinfer_sparse.h).  A forest keeps a host
 // copy of the descriptor arrays the layout-1 packer reads; the first CSR call
-// packs them, derives the sparse image and uploads it to every replica.
+// packs them, derives the sparse image and uploads it to every replica.  The
+// first small batch (treeinfer_small.h) packs the same copy for the layout-1
+// set alone; a forest neither walk serves keeps no copy.
 void keep_sparse_source(const ti_forest_desc* d, ti_forest* f) {
   if (d->lin_offset) f->sparse_refused = "CSR rows of a forest with linear leaves (a leaf's model reads raw columns)";
   else if (d->n_pre_steps > 0) f->sparse_refused = "CSR rows of a forest with pre-steps (they transform every element, stored or not)";
   else if (d->tree_weight) f->sparse_refused = "CSR rows of a forest with tree weights (its quantile kind has no CSR walk)";
-  if (!f->sparse_refused.empty()) return;
+  f->small_routed = d->lin_offset != nullptr || d->n_pre_steps > 0;
+  if (f->small_routed) return;
   auto src = std::make_unique<ti_forest::SparseSource>();
   const int64_t N = d->n_nodes, T = d->n_trees;
   src->tree_offset.assign(d->tree_offset, d->tree_offset + T + 1);
@@ -840,6 +845,7 @@ void keep_sparse_source(const ti_forest_desc* d, ti_forest* f) {
   src->desc.cover = d->cover ? src->cover.data() : nullptr;
   src->desc.tree_group = nullptr;   // every replica holds the groups already
   src->desc.base_margin = nullptr;
+  src->desc.tree_weight = nullptr;   // the packer reads none; a weighted forest walks small batches
   if (f->has_cat) {
     src->cat_bits.assign(d->cat_bits, d->cat_bits + d->n_cat_words);
     src->cat_offset.assign(d->cat_offset, d->cat_offset + N);
@@ -851,23 +857,111 @@ void keep_sparse_source(const ti_forest_desc* d, ti_forest* f) {
   f->sparse_src = std::move(src);
 }
 
+// Runs `work(replica)` with each replica's device current, stopping at the
+// first failure; then `undo(replica)` on every replica with its byte count put
+// back, so that nothing half-built survives.  The caller's device is current
+// again afterwards.
+template <typename Work, typename Undo>
+int on_each_replica(ti_forest* f, Work work, Undo undo) {
+  int dev0 = 0;
+  TI_HIP(hipGetDevice(&dev0));
+  int rc = TI_OK;
+  std::vector<int64_t> bytes0;
+  for (auto& dp : f->devs) bytes0.push_back(dp->bytes);
+  for (auto& dp : f->devs) {
+    if ((rc = fail_hip(hipSetDevice(dp->device), "hipSetDevice"))) break;
+    if ((rc = work(*dp))) break;
+  }
+  if (rc) {
+    const std::string err = g_last_error;
+    for (size_t i = 0; i < f->devs.size(); ++i) {
+      (void)hipSetDevice(f->devs[i]->device);
+      undo(*f->devs[i]);
+      f->devs[i]->bytes = bytes0[i];
+    }
+    (void)hipGetLastError();
+    (void)hipSetDevice(dev0);
+    return fail(rc, err);
+  }
+  TI_HIP(hipSetDevice(dev0));
+  return TI_OK;
+}
+
+// The layout-1 set of the forest, packed from its source into *h.  A forest of
+// leaves alone gets one node nobody follows, so that every clamped node load
+// has a target; *share: a layout-1 forest with an internal node, whose resident
+// arrays are that set.
+void pack_explicit_set(const ti_forest* f, HostImage* h, bool* share) {
+  with_acc(f->accum, [&](auto acc) {
+    pack_explicit<decltype(acc)>(&f->sparse_src->desc, h);
+    return true;
+  });
+  *share = f->layout == kLayoutExplicit && !h->nodes.empty();
+  if (h->nodes.empty()) {
+    h->nodes.push_back(ExpNode{0.0f, 0u, ~0, ~0});
+    h->thr64.push_back(0.0);
+  }
+}
+
+// SparsePtrs::sp_ex on every replica, once a forest: the CSR walk and the
+// small-batch walk share it.  shap_mu is held; h and share are
+// pack_explicit_set's.  The bytes count in ti_forest_info.device_bytes.
+int ensure_explicit_set(ti_forest* f, const HostImage& h, bool share) {
+  if (f->ex_ready.load(std::memory_order_relaxed)) return TI_OK;
+  const int rc = on_each_replica(
+      f,
+      [&](DeviceForest& d) {
+        if (share) {
+          d.sp_ex = {d.nodes, d.thr64, d.node_base, d.root, d.leaf_base, d.leaves, d.exp_leaf_ids, d.cat_words};
+          return TI_OK;
+        }
+        int rc = TI_OK;
+        auto up = [&](auto** dst, const auto& src) {
+          if (rc == TI_OK) rc = upload(&d.ex_mem, dst, src, &d.bytes);
+        };
+        up(&d.sp_ex.nodes, h.nodes);
+        up(&d.sp_ex.thr64, h.thr64);
+        up(&d.sp_ex.node_base, h.node_base);
+        up(&d.sp_ex.root, h.root);
+        up(&d.sp_ex.leaf_base, h.leaf_base);
+        up(&d.sp_ex.leaves, h.leaves);
+        up(&d.sp_ex.exp_leaf_ids, h.exp_leaf_ids);
+        up(&d.sp_ex.cat_words, h.cat_words);
+        return rc;
+      },
+      [](DeviceForest& d) {
+        d.ex_mem.release();
+        d.sp_ex = SparsePtrs::Explicit();
+      });
+  if (rc) return rc;
+  f->sparse_node_last = static_cast<int64_t>(h.nodes.size()) - 1;
+  f->ex_ready.store(true, std::memory_order_release);
+  return TI_OK;
+}
+
+// The first small batch: the layout-1 set alone.  The source goes with it
+// where no CSR call can follow.
+int ensure_small(ti_forest* f) {
+  if (f->ex_ready.load(std::memory_order_acquire)) return TI_OK;
+  std::lock_guard<std::mutex> lk(f->shap_mu);
+  if (f->ex_ready.load(std::memory_order_relaxed)) return TI_OK;
+  HostImage h;
+  bool share = false;
+  pack_explicit_set(f, &h, &share);
+  const int rc = ensure_explicit_set(f, h, share);
+  if (rc == TI_OK && !f->sparse_refused.empty()) f->sparse_src.reset();
+  return rc;
+}
+
 int ensure_sparse(ti_forest* f) {
   if (f->sparse_ready.load(std::memory_order_acquire)) return TI_OK;
   std::lock_guard<std::mutex> lk(f->shap_mu);
   if (f->sparse_ready.load(std::memory_order_relaxed)) return TI_OK;
   HostImage h;
-  with_acc(f->accum, [&](auto acc) {
-    pack_explicit<decltype(acc)>(&f->sparse_src->desc, &h);
-    return true;
-  });
-  // a layout-1 forest with an internal node walks its resident arrays; every
-  // other forest gets the packed set of its own.  A forest of leaves alone
-  // gets one node nobody follows, so that every clamped node load has a target.
-  const bool share = f->layout == kLayoutExplicit && !h.nodes.empty();
-  if (h.nodes.empty()) {
-    h.nodes.push_back(ExpNode{0.0f, 0u, ~0, ~0});
-    h.thr64.push_back(0.0);
-  }
+  bool share = false;
+  pack_explicit_set(f, &h, &share);
+  int rc = ensure_explicit_set(f, h, share);
+  if (rc) return rc;
   std::vector<int32_t> slot_of_col(f->F, -1), cols;
   for (const ExpNode& e : h.nodes)
     if (static_cast<int32_t>(e.meta & ti::kMetaFeatMask) < f->F) slot_of_col[e.meta & ti::kMetaFeatMask] = 0;
@@ -880,49 +974,28 @@ int ensure_sparse(ti_forest* f) {
   for (ExpNode& e : slot_nodes)
     e.meta = (e.meta & ~ti::kMetaFeatMask) |
              (cols.empty() ? 0u : static_cast<uint32_t>(slot_of_col[e.meta & ti::kMetaFeatMask]));
-  int dev0 = 0;
-  TI_HIP(hipGetDevice(&dev0));
-  int rc = TI_OK;
-  std::vector<int64_t> bytes0;
-  for (auto& dp : f->devs) bytes0.push_back(dp->bytes);
-  for (auto& dp : f->devs) {
-    DeviceForest& d = *dp;
-    if ((rc = fail_hip(hipSetDevice(d.device), "hipSetDevice"))) break;
-    auto up = [&](auto** dst, const auto& src) {
-      if (rc == TI_OK) rc = upload(&d.sparse_mem, dst, src, &d.bytes);
-    };
-    up(&d.sp_slot_nodes, slot_nodes);
-    up(&d.sp_cols, cols);
-    up(&d.sp_slot_of_col, slot_of_col);
-    if (share) {
-      d.sp_ex = {d.nodes, d.thr64, d.node_base, d.root, d.leaf_base, d.leaves, d.exp_leaf_ids, d.cat_words};
-    } else {
-      up(&d.sp_ex.nodes, h.nodes);
-      up(&d.sp_ex.thr64, h.thr64);
-      up(&d.sp_ex.node_base, h.node_base);
-      up(&d.sp_ex.root, h.root);
-      up(&d.sp_ex.leaf_base, h.leaf_base);
-      up(&d.sp_ex.leaves, h.leaves);
-      up(&d.sp_ex.exp_leaf_ids, h.exp_leaf_ids);
-      up(&d.sp_ex.cat_words, h.cat_words);
-    }
-    if (rc) break;
-  }
-  if (rc) {   // nothing half-built survives; the source stays for the next call
-    const std::string err = g_last_error;
-    for (size_t i = 0; i < f->devs.size(); ++i) {
-      (void)hipSetDevice(f->devs[i]->device);
-      f->devs[i]->sparse_mem.release();
-      static_cast<SparsePtrs&>(*f->devs[i]) = SparsePtrs();
-      f->devs[i]->bytes = bytes0[i];
-    }
-    (void)hipGetLastError();
-    (void)hipSetDevice(dev0);
-    return fail(rc, err);
-  }
-  TI_HIP(hipSetDevice(dev0));
+  // the image's own arrays; the layout-1 set above stays whatever becomes of
+  // them (a small batch may be walking it), and the source for the next call
+  rc = on_each_replica(
+      f,
+      [&](DeviceForest& d) {
+        int rc = TI_OK;
+        auto up = [&](auto** dst, const auto& src) {
+          if (rc == TI_OK) rc = upload(&d.sparse_mem, dst, src, &d.bytes);
+        };
+        up(&d.sp_slot_nodes, slot_nodes);
+        up(&d.sp_cols, cols);
+        up(&d.sp_slot_of_col, slot_of_col);
+        return rc;
+      },
+      [](DeviceForest& d) {
+        d.sparse_mem.release();
+        d.sp_slot_nodes = nullptr;
+        d.sp_cols = nullptr;
+        d.sp_slot_of_col = nullptr;
+      });
+  if (rc) return rc;
   f->sparse_U = static_cast<int32_t>(cols.size());
-  f->sparse_node_last = static_cast<int64_t>(h.nodes.size()) - 1;
   f->sparse_src.reset();
   f->sparse_ready.store(true, std::memory_order_release);
   return TI_OK;
@@ -964,6 +1037,63 @@ int plan_sparse(const ti_forest* f, const DeviceForest& d, int xdt, int kind, in
   a.sp_U = f->sparse_U;
   a.sp_absent_nan = absent == TI_CSR_ABSENT_NAN;
   a.sp_node_last = f->sparse_node_last;
+  return TI_OK;
+}
+
+// -------------------------------------------------------------- small batches
+// TI_OPT_SMALL_BATCH_ROWS (treeinfer_small.h): whether a launch
+// of `rows` rows and this kind leaves the forest's own walk for the
+// tree-parallel one.  The option is read here, every call.  A grid of one
+// workgroup a row holds fewer than 2^32 lanes; whatever the option says, more
+// rows than that keep the forest's own walk.
+int small_block(const ti_forest* f) { return std::min(ti::kSmallMaxBlock, (f->T + 63) & ~63); }
+
+bool small_takes(const ti_forest* f, int64_t rows, int kind) {
+  if (f->small_routed || !f->parts.empty()) return false;
+  if (kind != TI_OUTPUT_MARGIN && kind != TI_OUTPUT_PREDICT && kind != TI_OUTPUT_LEAF) return false;
+  const int64_t grid_max = ((int64_t(1) << 32) - 1) / small_block(f);
+  return rows >= 1 && rows <= std::min(f->small_rows.load(), grid_max);
+}
+
+// A workgroup a row, a lane a tree: min(1024, T rounded up to 64) lanes.  The
+// row goes to LDS while it fits the feature budget of the other walks.
+void plan_small(const ti_forest* f, const DeviceForest& d, int xdt, int kind, LaunchPlan* p) {
+  plan_model(f, d, xdt, kind, p);
+  p->R = 1;
+  p->block = small_block(f);
+  const size_t fb = ti::small_feat_bytes(f->F, dtype_size(xdt));
+  p->key.walk = ti::Walk::TreeLanes;
+  p->key.feat_lds = fb <= kFeatLdsMax;
+  p->lds = ti::small_lds_bytes(p->key.feat_lds ? fb : 0, p->block);
+  KArgs& a = p->a;
+  a.nodes = d.sp_ex.nodes;
+  a.thr64 = d.sp_ex.thr64;
+  a.node_base = d.sp_ex.node_base;
+  a.root = d.sp_ex.root;
+  a.leaf_base = d.sp_ex.leaf_base;
+  a.leaves = d.sp_ex.leaves;
+  a.exp_leaf_ids = d.sp_ex.exp_leaf_ids;
+  a.cat_words = d.sp_ex.cat_words;
+  a.sp_node_last = f->sparse_node_last;
+}
+
+int launch_small(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows, int32_t cols,
+                 int64_t stride, int kind, void* out, hipStream_t stream) {
+  int rc = ensure_small(f);
+  if (rc) return rc;
+  LaunchPlan p;
+  plan_small(f, d, xdt, kind, &p);
+  p.a.X = X;
+  p.a.n_rows = rows;
+  p.a.row_stride = stride;
+  p.a.n_cols = cols;
+  p.a.out = out;
+  KernelFn fn = ti::select(p.key);
+  if ((rc = ensure_lds_attr(d.device, fn))) return rc;
+  occ_note(fn, p.block, p.lds);
+  hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(rows)), dim3(p.block), p.lds, stream, p.a);
+  TI_HIP(hipGetLastError());
+  f->small_served.store(true, std::memory_order_relaxed);
   return TI_OK;
 }
 
@@ -1495,6 +1625,8 @@ int launch_walk(ti_forest* f, int slot, const void* X, int xdt, int64_t rows, in
     return launch_chunked(f, slot, X, xdt, rows, cols, stride, kind, out, stream);
   if (f->linear && (kind == TI_OUTPUT_MARGIN || kind == TI_OUTPUT_PREDICT))
     return launch_linear(f, *f->devs[slot], X, xdt, rows, cols, stride, kind, out, stream);
+  if (small_takes(f, rows, kind))
+    return launch_small(f, *f->devs[slot], X, xdt, rows, cols, stride, kind, out, stream);
   return launch(f, *f->devs[slot], X, xdt, rows, cols, stride, kind, out, stream);
 }
 
@@ -1565,6 +1697,7 @@ int create_chunked(const ti_forest_desc* d, const std::vector<int>& depth, const
   // the part loop hands each part dense device rows; it has no CSR form
   f->sparse_refused = "CSR rows of a forest served in group parts (more than " +
                       std::to_string(ti::kMaxGroups) + " output groups)";
+  f->small_routed = true;
   const int K = d->n_groups, LW = d->leaf_width;
   for (int k0 = 0; k0 < K; k0 += ti::kMaxGroups) {
     const int kc = std::min(ti::kMaxGroups, K - k0);
@@ -1632,6 +1765,8 @@ int create_chunked(const ti_forest_desc* d, const std::vector<int>& depth, const
       return rc;
     }
     part->pre_steps = 0;   // the parent transforms X once (launch_any); no part does
+    part->small_routed = true;   // the part loop keeps each part's own walk,
+    part->sparse_src.reset();    // so neither shared walk ever packs a part's copy
     part->quant_tab.reset();   // nor is a part asked for quantiles: the parent refuses them
     part->quant_refused = f->quant_refused;
     f->parts.emplace_back(part);
@@ -1813,6 +1948,8 @@ int ti_forest_get_info(const ti_forest* f, ti_forest_info* info) {
     info->sparse_walk[i] = !sp ? 0 : t.search ? 2 : 1;
     info->sparse_rows[i] = sp ? t.R : 0;
   }
+  info->small_walk = f->small_routed ? -1
+                     : f->ex_ready.load(std::memory_order_acquire) && f->small_served.load() ? 1 : 0;
   return TI_OK;
 }
 
@@ -1839,6 +1976,10 @@ int ti_forest_set_option(ti_forest* f, int32_t option, int64_t value) {
     case TI_OPT_LINEAR_SCRATCH_MB:
       if (value < 0) return fail(TI_ERR_INVALID, "TI_OPT_LINEAR_SCRATCH_MB must be >= 0");
       f->lin_scratch_mb.store(std::min<int64_t>(value, int64_t(1) << 30));
+      return TI_OK;
+    case TI_OPT_SMALL_BATCH_ROWS:
+      if (value < 0) return fail(TI_ERR_INVALID, "TI_OPT_SMALL_BATCH_ROWS must be >= 0");
+      f->small_rows.store(value);
       return TI_OK;
     default:
       return fail(TI_ERR_INVALID, "unknown option " + std::to_string(option));

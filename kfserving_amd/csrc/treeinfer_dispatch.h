@@ -2,8 +2,9 @@
 // treeinfer_k_<x><a>.hip instantiates every kernel of one (input type,
 // accumulator type) pair, treeinfer_k_cat.hip the categorical heap's,
 // treeinfer_k_crec.hip the categorical records', treeinfer_k_obliv.hip the
-// oblivious trees' and treeinfer_k_sparse.hip the CSR walk's for all four pairs,
-// so the eight compile in parallel.
+// oblivious trees', treeinfer_k_sparse.hip the CSR walk's and
+// treeinfer_k_small.hip the small-batch walk's for all four pairs, so the nine
+// compile in parallel.
 //
 // The host names what it launches with a KernelKey; ti::select(key) is the one
 // way from a key to a kernel.  Each rule that turns a runtime value into a
@@ -41,13 +42,14 @@ enum class Walk {
   ObliviousGather,  // 12: ... some tables gathered              (treeinfer_obliv.h)
   SparseImage,      // CSR rows, the used columns in an LDS image  sparse_explicit_predict_kernel
   SparseSearch,     // CSR rows, each column searched in its row   (treeinfer_sparse.h)
+  TreeLanes,        // small batches: a lane a tree, a workgroup a row  tree_lanes_predict_kernel
 };
 
 struct KernelKey {
   Walk walk;
   bool x64, acc64;   // float64 input / sums (else float32)
   int K;             // output groups
-  bool feat_lds;     // Heap, Explicit: feature image in LDS
+  bool feat_lds;     // Heap, Explicit: feature image in LDS; TreeLanes: the row in LDS
   bool zero_rule;    // LightGBM zero rule (no binned heap walk has one)
   bool bins16;       // BinHeap, BinHeapFixed, HeapTopStaged: u16 bins (else u8)
   int ilp;           // record walks and bottoms: trees a lane walks at once
@@ -149,6 +151,8 @@ KernelFn select_walk(const KernelKey& k) {
     case Walk::SparseImage:
     case Walk::SparseSearch:
       break;   // kernels_sparse
+    case Walk::TreeLanes:
+      break;   // kernels_small
   }
   return nullptr;
 }
@@ -168,12 +172,14 @@ KernelFn kernels_cat(const KernelKey& k);   // the categorical heap, every pair
 KernelFn kernels_crec(const KernelKey& k);  // the categorical records, every pair
 KernelFn kernels_obliv(const KernelKey& k); // the oblivious trees, every pair
 KernelFn kernels_sparse(const KernelKey& k);// the CSR walk, every pair
+KernelFn kernels_small(const KernelKey& k); // the small-batch walk, every pair
 
 inline KernelFn select(const KernelKey& k) {
   if (k.walk == Walk::CatHeapXgb || k.walk == Walk::CatHeapLgb) return kernels_cat(k);
   if (k.walk == Walk::CatRecordXgb || k.walk == Walk::CatRecordLgb) return kernels_crec(k);
   if (k.walk == Walk::Oblivious || k.walk == Walk::ObliviousGather) return kernels_obliv(k);
   if (k.walk == Walk::SparseImage || k.walk == Walk::SparseSearch) return kernels_sparse(k);
+  if (k.walk == Walk::TreeLanes) return kernels_small(k);
   if (!k.x64) return k.acc64 ? kernels_fd(k) : kernels_ff(k);
   return k.acc64 ? kernels_dd(k) : kernels_df(k);
 }

@@ -116,7 +116,8 @@ bool dev_knobs() {
 }
 
 bool operational_knob(const char* name) {
-  static const char* const kOps[] = {"TI_CHUNK_MB", "TI_SHAP_TABLE_ROWS", "TI_SHAP_TABLE_MB"};
+  static const char* const kOps[] = {"TI_CHUNK_MB", "TI_SHAP_TABLE_ROWS", "TI_SHAP_TABLE_MB",
+                                     "TI_SMALL_BATCH_ROWS"};
   for (const char* k : kOps)
     if (std::strcmp(k, name) == 0) return true;
   return false;
@@ -314,7 +315,9 @@ struct QuantilePtrs {
 // The sparse image of ti_predict_csr (treeinfer_sparse.h: ensure_sparse).  The
 // slot nodes, the used columns and slot_of_col are the image's own; ex is the
 // layout-1 set both regimes walk beside them: a layout-1 forest's resident
-// arrays (not owned), or uploads of the image's own for every other layout.
+// arrays (not owned), or uploads of its own for every other layout (ex_mem).
+// The small-batch walk (treeinfer_small.h) walks the same set: whichever of the
+// two needs it first uploads it (ensure_explicit_set), once.
 struct SparsePtrs {
   ExpNode* sp_slot_nodes = nullptr;    // layout-1 nodes with the slot in the feature field
   int32_t* sp_cols = nullptr;          // [U] sorted
@@ -386,7 +389,7 @@ struct CallScratch {
 struct DeviceForest : ForestPtrs, ShapPtrs, ApproxPtrs, QuantilePtrs, SparsePtrs, ScratchBufs {
   int device = -1;
   hipStream_t stream = nullptr;
-  DeviceAllocs forest_mem, shap_mem, approx_mem, quant_mem, sparse_mem;
+  DeviceAllocs forest_mem, shap_mem, approx_mem, quant_mem, sparse_mem, ex_mem;
   std::atomic<int32_t> shap_tab_state{0};   // 0 not tried, 1 built, -1 failed or over the cap:
                                      // contributions use the extend / unwind kernel
   // TI_OUTPUT_INTERACT scratch (launch_interact: contributions + partials of
@@ -705,7 +708,19 @@ struct ti_forest {
   std::string sparse_refused;
   std::atomic<bool> sparse_ready{false};
   int32_t sparse_U = 0;
+  // The layout-1 set (SparsePtrs::sp_ex) the CSR walk and the small-batch walk
+  // share: uploaded by whichever comes first (ensure_explicit_set, under
+  // shap_mu).  The host copy below stays while a later CSR call may still derive
+  // its slot nodes from it.
+  std::atomic<bool> ex_ready{false};
   int64_t sparse_node_last = 0;   // last index of the (padded) node arrays
+  // Small batches (TI_OPT_SMALL_BATCH_ROWS, treeinfer_small.h): a launch of
+  // 1 .. small_rows rows takes the tree-parallel walk; 0: never.  small_routed:
+  // the forest keeps its own path whatever the option says (linear leaves,
+  // pre-steps, a group part); small_served: the walk has answered a call.
+  std::atomic<int64_t> small_rows{std::max(env_int("TI_SMALL_BATCH_ROWS", 0), 0)};
+  bool small_routed = false;
+  std::atomic<bool> small_served{false};
   struct SparseSource {
     ti_forest_desc desc;
     std::vector<int64_t> tree_offset, cat_offset;

@@ -21,7 +21,7 @@ import numpy as np
 from .forest import (Forest, OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_CONTRIB_INTERV, OUT_INTERACT,
                      OUT_LEAF, OUT_MARGIN, OUT_PREDICT, OUT_TREE_QUANTILE, TI_F32, TI_F64, TI_I32)
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 _LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("TREEINFER_LIB", os.path.join(_LIB_DIR, "libtreeinfer.so"))
 
@@ -40,6 +40,7 @@ OPT_SHAP_TABLE_ROWS = 1
 OPT_SHAP_TABLE_MB = 2
 OPT_HOST_REGISTER = 3
 OPT_LINEAR_SCRATCH_MB = 4
+OPT_SMALL_BATCH_ROWS = 5
 
 
 class TreeInferError(RuntimeError):
@@ -117,6 +118,7 @@ class _ForestInfo(ctypes.Structure):
         ("sparse_cols", ctypes.c_int32),
         ("sparse_walk", ctypes.c_int32 * 2),
         ("sparse_rows", ctypes.c_int32 * 2),
+        ("small_walk", ctypes.c_int32),
     ]
 
 
@@ -289,7 +291,8 @@ class DeviceForest:
     def set_option(self, option: int, value: int) -> None:
         """ti_forest_set_option: speed knobs that never change results
         (OPT_SHAP_TABLE_ROWS, OPT_SHAP_TABLE_MB, OPT_HOST_REGISTER,
-        OPT_LINEAR_SCRATCH_MB)."""
+        OPT_LINEAR_SCRATCH_MB, OPT_SMALL_BATCH_ROWS: batches of at most that
+        many rows take the tree-parallel walk, 0 never)."""
         _check(self._lib, self._lib.ti_forest_set_option(self._handle, option, int(value)))
 
     def set_background(self, Z) -> None:
@@ -442,6 +445,7 @@ class DeviceForest:
 
 __all__ = ["DeviceForest", "TreeInferError", "prepare_input", "load_library", "device_count", "default_devices",
            "OPT_SHAP_TABLE_ROWS", "OPT_SHAP_TABLE_MB", "OPT_HOST_REGISTER", "OPT_LINEAR_SCRATCH_MB",
+           "OPT_SMALL_BATCH_ROWS",
            "EXPORTED_SYMBOLS", "OUT_MARGIN", "OUT_PREDICT", "OUT_LEAF", "OUT_CONTRIB", "OUT_INTERACT",
            "OUT_CONTRIB_APPROX", "OUT_CONTRIB_INTERV", "OUT_TREE_QUANTILE",
            "TI_F32", "TI_F64", "TI_I32"]
