@@ -126,6 +126,21 @@
  * bits of the forest's own walk.  Forests with linear leaves, pre-steps or more
  * than 16 output groups, every other output kind and CSR rows keep their path
  * (ti_forest_info.small_walk).
+ *
+ * Staged predictions (ABI 14; TI_OUTPUT_STAGED: xgboost's iteration_range /
+ * ntree_limit, LightGBM's start_iteration / num_iteration, sklearn's staged_*):
+ * with the stages begin, ends[0] < ... < ends[S-1] of ti_forest_set_stages, stage
+ * s of a row is what the forest made of the trees [begin, ends[s]) alone, every
+ * other field of the descriptor kept, writes for that row as TI_OUTPUT_MARGIN
+ * (transformed = 0) or TI_OUTPUT_PREDICT (transformed = 1), bit for bit.  So the
+ * base margin is in every stage; base_first = 0 forms base + acc at each stage;
+ * average_divisor is applied as the forest holds it -- the forest's, not the
+ * stage's tree count: a stage of an averaging forest is its partial sum over
+ * the whole forest's T; pre-steps apply; vector leaves add to all K outputs;
+ * tree weights are ignored.  The margins are accumulated in tree order, one add
+ * a tree in the accumulator type, so a stage is a snapshot of the chain the
+ * whole forest runs, and the stages of one call cost one walk of the forest and
+ * one replay of the chain.
  */
 #ifndef TREEINFER_H_
 #define TREEINFER_H_
@@ -136,7 +151,7 @@
 extern "C" {
 #endif
 
-#define TI_ABI_VERSION 13
+#define TI_ABI_VERSION 14
 
 /* return codes */
 #define TI_OK               0
@@ -262,6 +277,23 @@ extern "C" {
                               /* host pipeline sizes its row chunks by the wider */
                               /* of the input row and the 4 * T bytes of leaf    */
                               /* ids a row takes between the two passes.         */
+#define TI_OUTPUT_STAGED 8
+                              /* ABI 14: the stages of ti_forest_set_stages (the  */
+                              /* rule above), [rows, S, W] in the accumulator     */
+                              /* type: W = K for margins, TI_OUTPUT_PREDICT's     */
+                              /* width (1 under TI_TRANSFORM_ARGMAX) when         */
+                              /* transformed.  Two calls give the same bits.      */
+                              /* TI_ERR_UNSUPPORTED, the handle serving on, for   */
+                              /* linear leaves (a leaf's value needs X), for more */
+                              /* than 16 output groups, for a tree whose leaf ids */
+                              /* are negative or not distinct, and from           */
+                              /* ti_predict_csr.  TI_OPT_SMALL_BATCH_ROWS does    */
+                              /* not route it: the first pass is the forest's own */
+                              /* walk at every size.  The first call uploads a    */
+                              /* leaf table, which ti_forest_info.device_bytes    */
+                              /* then counts.  The host pipeline sizes its row    */
+                              /* chunks by the widest of the input row, the 4 * T */
+                              /* bytes of leaf ids and the S * W outputs.         */
 
 /*
  * Canonical forest: host structure-of-arrays over the nodes of all trees,
@@ -457,6 +489,26 @@ int ti_forest_set_background(ti_forest* forest, const void* Z, int32_t z_dtype,
  * per-tree predictions is np.quantile(..., method="inverted_cdf") over them. */
 int ti_forest_set_quantiles(ti_forest* forest, const double* q, int32_t n_q);
 
+/* ABI 14: the stages of TI_OUTPUT_STAGED.  begin and ends[] are tree indexes
+ * with 0 <= begin < ends[0] < ends[1] < ... < ends[n_stages-1] <= T and
+ * n_stages >= 1; transformed is 0 (stages as TI_OUTPUT_MARGIN) or 1 (as
+ * TI_OUTPUT_PREDICT).  Anything else is TI_ERR_INVALID and the forest keeps its
+ * stages.  The default is begin = 0, ends = {T}, transformed = 0: the whole
+ * forest's margin.  ti_output_shape reports n_rows * n_stages * W for the kind.
+ * Like ti_forest_set_quantiles it is handle state: it must be called with no
+ * TI_OUTPUT_STAGED call (and no ti_output_shape for that kind) in flight on the
+ * forest; no other kind reads the stages.  Each staged call copies the ends
+ * from the handle to the device on its stream (a host-to-device copy from
+ * pageable memory), so a ti_predict_device call of this kind cannot be
+ * recorded into a captured graph.  A tree index counts trees, not
+ * boosting iterations: an iteration of a multiclass model is n_groups (times
+ * num_parallel_tree) trees.  Replaces ntree_limit of XGBoosterPredict
+ * (iteration_range), num_iteration / start_iteration of
+ * LGBM_BoosterPredictForMat, and sklearn's staged_predict / staged_predict_proba
+ * / staged_decision_function, whose every stage is a predict of its own there. */
+int ti_forest_set_stages(ti_forest* forest, int32_t begin, const int32_t* ends,
+                         int32_t n_stages, int32_t transformed);
+
 /* Per-forest tuning that changes speed, never results (both TreeSHAP kernels
  * produce the same contributions).  0 or TI_ERR_INVALID for an unknown option
  * or a negative value.  Replaces nothing in the libraries: xgboost and
@@ -497,7 +549,7 @@ int ti_predict(ti_forest* forest, const void* X, int32_t x_dtype, int64_t n_rows
  * and TI_OUTPUT_LEAF of any forest the float explicit kernel can walk
  * (numerical splits, both categorical rules, vector leaves, multiclass groups,
  * either accumulator, lgb_zero_map).  TI_ERR_UNSUPPORTED, the handle serving
- * on, for every other output kind and for forests with linear leaves, pre-steps,
+ * on, for every other output kind (TI_OUTPUT_STAGED too) and for forests with linear leaves, pre-steps,
  * tree weights or more than 16 output groups (group parts).  The first call
  * builds the forest's sparse image on every device, which
  * ti_forest_info.device_bytes then counts.  Thread-safe per handle.

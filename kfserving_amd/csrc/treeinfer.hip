@@ -23,6 +23,7 @@
 #include "treeinfer_shap_interv.h"
 #include "treeinfer_approx.h"
 #include "treeinfer_quantile.h"
+#include "treeinfer_staged.h"
 #include "treeinfer_pre.h"
 #include "treeinfer_sparse.h"
 #include "treeinfer_small.h"
@@ -45,6 +46,11 @@ void free_scratch(DeviceForest& d) {
   static_cast<ScratchBufs&>(d) = ScratchBufs();
 }
 
+void free_staged(DeviceForest& d) {
+  d.staged_mem.release();
+  static_cast<StagedPtrs&>(d) = StagedPtrs();
+}
+
 void free_device(DeviceForest& d) {
   if (d.device < 0) return;
   (void)hipSetDevice(d.device);
@@ -54,6 +60,7 @@ void free_device(DeviceForest& d) {
   free_interv(d);
   free_approx(d);
   free_quantile(d);
+  free_staged(d);
   d.sparse_mem.release();
   d.ex_mem.release();
   static_cast<SparsePtrs&>(d) = SparsePtrs();
@@ -209,12 +216,19 @@ void occ_note(KernelFn fn, int block, size_t lds) {
                block, lds, n, n * ((block + 63) / 64) / 4, attr.numRegs, 0);
 }
 
+// Outputs of one stage of TI_OUTPUT_STAGED: the margin's, or the prediction's.
+int64_t stage_width(const ti_forest* f) {
+  return f->stage_transformed && f->transform == TI_TRANSFORM_ARGMAX ? 1 : f->K;
+}
+
 int64_t output_width(const ti_forest* f, int kind) {
   if (kind == TI_OUTPUT_LEAF) return f->T;
   if (kind == TI_OUTPUT_CONTRIB || kind == TI_OUTPUT_CONTRIB_APPROX || kind == TI_OUTPUT_CONTRIB_INTERV)
     return static_cast<int64_t>(f->K) * (f->F + 1);
   if (kind == TI_OUTPUT_INTERACT) return static_cast<int64_t>(f->K) * (f->F + 1) * (f->F + 1);
   if (kind == TI_OUTPUT_TREE_QUANTILE) return static_cast<int64_t>(f->quant_q.size());
+  if (kind == TI_OUTPUT_STAGED)
+    return static_cast<int64_t>(f->stage_ends.size()) * stage_width(f);
   if (kind == TI_OUTPUT_PREDICT && f->transform == TI_TRANSFORM_ARGMAX) return 1;
   return f->K;
 }
@@ -586,14 +600,16 @@ int64_t chunk_rows(size_t row_bytes) {
 // same with their K * (F + 1) outputs (their pass 2 has 64-row tiles too).
 // Quantiles across trees write a few elements a row, but a row holds 4 * T
 // bytes of leaf ids between the two passes: that scratch row takes the output
-// row's place.
+// row's place.  Staged predictions hold the same scratch row and write S * W
+// elements a row: the wider of the two counts.
 int64_t chunk_rows_for(const ti_forest* f, int xdt, int64_t stride, int kind) {
   const size_t x_row = static_cast<size_t>(stride) * dtype_size(xdt);
-  if (kind != TI_OUTPUT_INTERACT && kind != TI_OUTPUT_CONTRIB_APPROX && kind != TI_OUTPUT_TREE_QUANTILE)
+  if (kind != TI_OUTPUT_INTERACT && kind != TI_OUTPUT_CONTRIB_APPROX && kind != TI_OUTPUT_TREE_QUANTILE &&
+      kind != TI_OUTPUT_STAGED)
     return chunk_rows(x_row);
-  const size_t o_row = kind == TI_OUTPUT_TREE_QUANTILE
-                           ? static_cast<size_t>(4) * f->T
-                           : dtype_size(output_dtype(f, kind)) * static_cast<size_t>(output_width(f, kind));
+  size_t o_row = dtype_size(output_dtype(f, kind)) * static_cast<size_t>(output_width(f, kind));
+  if (kind == TI_OUTPUT_TREE_QUANTILE) o_row = static_cast<size_t>(4) * f->T;
+  if (kind == TI_OUTPUT_STAGED) o_row = std::max(o_row, static_cast<size_t>(4) * f->T);
   const int mb = env_int("TI_CHUNK_MB", 64);
   const int64_t r = static_cast<int64_t>((static_cast<size_t>(std::max(mb, 1)) << 20) /
                                          std::max<size_t>(std::max(x_row, o_row), 1));
@@ -1590,6 +1606,164 @@ int launch_quantile(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64
   return rc;
 }
 
+// Staged predictions (treeinfer_staged.h; the default stages are fill_model's).
+// At create: whether the kind is possible, and the host leaf table ensure_staged uploads on
+// first use: per (tree, leaf id) the leaf_width values in the accumulator type,
+// converted as the packers convert them, so float32 leaves are never widened.
+// A float64 forest of one scalar output that the quantile kind serves reads
+// that kind's tables (the same values at the same addresses) and builds none.
+// The host table is a copy of every leaf value in the accumulator type (LW x
+// 4 or 8 bytes a leaf id) that a handle keeps until its first staged call, as
+// the quantile tables are kept: the descriptor is gone after create, so it
+// cannot be built later.
+void keep_staged_source(const ti_forest_desc* d, ti_forest* f) {
+  auto refuse = [&](const std::string& why) { f->staged_refused = "TI_OUTPUT_STAGED " + why; };
+  if (d->lin_offset) return refuse("of a forest with linear leaves (a leaf's value needs X)");
+  if (d->n_groups > ti::kMaxGroups)
+    return refuse("serves at most " + std::to_string(ti::kMaxGroups) + " output groups, the forest has " +
+                  std::to_string(d->n_groups));
+  if (d->accum_dtype == TI_F64 && d->leaf_width == 1 && d->n_groups == 1 && f->quant_refused.empty()) {
+    f->staged_shared = true;
+    return;
+  }
+  auto tab = std::make_unique<ti_forest::StagedTables>();
+  const int T = d->n_trees, LW = d->leaf_width;
+  const size_t es = d->accum_dtype == TI_F64 ? 8 : 4;
+  tab->leaf_base.assign(T + 1, 0);
+  int64_t total = 0;
+  for (int t = 0; t < T; ++t) {
+    int64_t top = -1;
+    for (int64_t g = d->tree_offset[t]; g < d->tree_offset[t + 1]; ++g)
+      if (d->feature[g] < 0) {
+        if (d->leaf_id[g] < 0) top = INT64_MAX;
+        top = std::max<int64_t>(top, d->leaf_id[g]);
+      }
+    // distinct ids: every slot of the tree's range is written at most once
+    std::vector<char> seen(top == INT64_MAX || top < 0 ? 0 : static_cast<size_t>(top) + 1, 0);
+    bool distinct = top != INT64_MAX;
+    if (distinct) {
+      tab->leaves.resize(static_cast<size_t>(total + top + 1) * LW * es);
+      for (int64_t g = d->tree_offset[t]; g < d->tree_offset[t + 1] && distinct; ++g)
+        if (d->feature[g] < 0) {
+          if (seen[d->leaf_id[g]]) distinct = false;
+          seen[d->leaf_id[g]] = 1;
+          unsigned char* at = tab->leaves.data() + static_cast<size_t>(total + d->leaf_id[g]) * LW * es;
+          for (int k = 0; k < LW; ++k) {
+            const double v = d->leaf_value[g * LW + k];
+            const float v32 = static_cast<float>(v);
+            if (es == 8) std::memcpy(at + k * 8, &v, 8);
+            else std::memcpy(at + k * 4, &v32, 4);
+          }
+        }
+      // an id that names no leaf reads NaN, as the quantile tables have it
+      for (size_t i = 0; i < seen.size(); ++i)
+        if (!seen[i])
+          for (int k = 0; k < LW; ++k) {
+            const double nan64 = std::numeric_limits<double>::quiet_NaN();
+            const float nan32 = std::numeric_limits<float>::quiet_NaN();
+            unsigned char* at = tab->leaves.data() + (static_cast<size_t>(total + i) * LW + k) * es;
+            if (es == 8) std::memcpy(at, &nan64, 8);
+            else std::memcpy(at, &nan32, 4);
+          }
+    }
+    if (!distinct)
+      return refuse("finds a tree's values by its leaf id: tree " + std::to_string(t) +
+                    " has leaf ids that are negative or not distinct");
+    total += top + 1;
+    tab->leaf_base[t + 1] = total;
+  }
+  f->staged_tab = std::move(tab);
+}
+
+// First TI_OUTPUT_STAGED call of a handle: the tables go to every replica,
+// under the forest's lock (ensure_quantile's lifecycle; the shared tables are
+// that function's own).
+int ensure_staged(ti_forest* f) {
+  if (f->staged_ready.load(std::memory_order_acquire)) return TI_OK;
+  if (f->staged_shared) {
+    const int rc = ensure_quantile(f);
+    if (rc == TI_OK) f->staged_ready.store(true, std::memory_order_release);
+    return rc;
+  }
+  std::lock_guard<std::mutex> lk(f->shap_mu);
+  if (f->staged_ready.load(std::memory_order_relaxed)) return TI_OK;
+  const ti_forest::StagedTables& tab = *f->staged_tab;
+  const int rc = on_each_replica(
+      f,
+      [&](DeviceForest& d) {
+        const int r = upload(&d.staged_mem, &d.staged_leaf_base, tab.leaf_base, &d.bytes);
+        return r ? r : upload(&d.staged_mem, &d.staged_leaves, tab.leaves, &d.bytes);
+      },
+      [](DeviceForest& d) { free_staged(d); });
+  if (rc) return rc;
+  f->staged_tab.reset();
+  f->staged_ready.store(true, std::memory_order_release);
+  return TI_OK;
+}
+
+// Two stream-ordered passes per row block, as launch_quantile has: the
+// forest's own walk with TI_OUTPUT_LEAF into a [rows_block, T] int32 scratch of
+// at most 1 GiB (the small-batch option does not route it), then
+// staged_accum_kernel, planned and selected like every walk.  The stage ends
+// ride behind the ids in the same scratch; they are copied from the handle,
+// which ti_forest_set_stages may not change while the call is in flight.
+int launch_staged(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows, int32_t cols,
+                  int64_t stride, void* out, hipStream_t stream) {
+  if (!f->staged_refused.empty()) return fail(TI_ERR_UNSUPPORTED, f->staged_refused);
+  if (rows <= 0) return TI_OK;
+  int rc = ensure_staged(f);
+  if (rc) return rc;
+  const int T = f->T;
+  const int S = static_cast<int>(f->stage_ends.size());
+  const int W = static_cast<int>(stage_width(f));
+  const size_t xs = dtype_size(xdt), as = dtype_size(f->accum);
+  LaunchPlan p;
+  plan_model(f, d, xdt, f->stage_transformed ? TI_OUTPUT_PREDICT : TI_OUTPUT_MARGIN, &p);
+  p.key.walk = ti::Walk::StagedAccum;
+  p.key.vector_leaf = f->LW > 1;
+  p.R = ti::kStRows;
+  p.block = ti::kStRows;
+  const int tile = ti::staged_tile_elems(W, as);
+  p.lds = ti::kStWaves * ti::staged_wave_lds(tile, as);
+  p.a.leaf_base = f->staged_shared ? d.quant_leaf_base : d.staged_leaf_base;
+  p.a.leaves = f->staged_shared ? static_cast<const void*>(d.quant_values) : d.staged_leaves;
+  p.a.st_begin = f->stage_begin;
+  p.a.st_n = S;
+  p.a.st_width = W;
+  p.a.st_tile = tile;
+  KernelFn fn = ti::select(p.key);
+  rc = ensure_lds_attr(d.device, fn);
+  if (rc) return rc;
+  occ_note(fn, p.block, p.lds);
+  const int64_t row_bytes = static_cast<int64_t>(4) * T;
+  int64_t rows_block = (int64_t(1) << 30) / row_bytes;
+  rows_block = std::max<int64_t>(p.R, rows_block / p.R * p.R);
+  const size_t ids_bytes = align16(static_cast<size_t>(std::min(rows, rows_block) * row_bytes));
+  ScratchHold buf(d, stream);   // given back behind the last pass 2
+  if (!buf.take(ids_bytes + static_cast<size_t>(S) * 4))
+    return fail(TI_ERR_NOMEM, "leaf-id scratch allocation failed");
+  int32_t* ids = static_cast<int32_t*>(buf.p);
+  int32_t* ends = reinterpret_cast<int32_t*>(static_cast<unsigned char*>(buf.p) + ids_bytes);
+  TI_HIP(hipMemcpyAsync(ends, f->stage_ends.data(), static_cast<size_t>(S) * 4, hipMemcpyHostToDevice, stream));
+  p.a.st_leaf_ids = ids;
+  p.a.st_ends = ends;
+  const size_t out_row = static_cast<size_t>(S) * W * as;
+  for (int64_t r0 = 0; r0 < rows && rc == TI_OK; r0 += rows_block) {
+    const int64_t nb = std::min(rows_block, rows - r0);
+    const void* xb = static_cast<const unsigned char*>(X) + static_cast<size_t>(r0 * stride) * xs;
+    rc = launch(f, d, xb, xdt, nb, cols, stride, TI_OUTPUT_LEAF, ids, stream);
+    if (rc) break;
+    p.a.n_rows = nb;
+    p.a.out = static_cast<unsigned char*>(out) + static_cast<size_t>(r0) * out_row;
+    const int64_t grid = (nb + p.R - 1) / p.R;
+    if (grid > 0x7fffffff) rc = fail(TI_ERR_INVALID, "too many rows for one launch");
+    if (rc) break;
+    hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(grid)), dim3(p.block), p.lds, stream, p.a);
+    if (hipGetLastError() != hipSuccess) rc = fail(TI_ERR_DEVICE, "staged accumulation launch failed");
+  }
+  return rc;
+}
+
 // The forest's walk of X as it stands: every kind, every forest shape.
 int launch_walk(ti_forest* f, int slot, const void* X, int xdt, int64_t rows, int32_t cols,
                 int64_t stride, int kind, void* out, hipStream_t stream) {
@@ -1599,6 +1773,10 @@ int launch_walk(ti_forest* f, int slot, const void* X, int xdt, int64_t rows, in
   if (kind == TI_OUTPUT_TREE_QUANTILE) {   // a forest in group parts has n_groups > 1: refused
     if (!f->parts.empty()) return fail(TI_ERR_UNSUPPORTED, f->quant_refused);
     return launch_quantile(f, *f->devs[slot], X, xdt, rows, cols, stride, out, stream);
+  }
+  if (kind == TI_OUTPUT_STAGED) {   // a forest in group parts is refused: more than 16 groups
+    if (!f->parts.empty()) return fail(TI_ERR_UNSUPPORTED, f->staged_refused);
+    return launch_staged(f, *f->devs[slot], X, xdt, rows, cols, stride, out, stream);
   }
   if (kind == TI_OUTPUT_CONTRIB && f->linear)
     return fail(TI_ERR_UNSUPPORTED,
@@ -1694,6 +1872,7 @@ int create_chunked(const ti_forest_desc* d, const std::vector<int>& depth, const
   fill_model(d, depth, f.get());
   f->lgb_zero_map = 0;   // the parts hold it: a parent launches no tree kernel
   keep_quantile_source(d, f.get());   // more than 16 groups: the refusal alone
+  keep_staged_source(d, f.get());     // the same
   // the part loop hands each part dense device rows; it has no CSR form
   f->sparse_refused = "CSR rows of a forest served in group parts (more than " +
                       std::to_string(ti::kMaxGroups) + " output groups)";
@@ -1769,6 +1948,8 @@ int create_chunked(const ti_forest_desc* d, const std::vector<int>& depth, const
     part->sparse_src.reset();    // so neither shared walk ever packs a part's copy
     part->quant_tab.reset();   // nor is a part asked for quantiles: the parent refuses them
     part->quant_refused = f->quant_refused;
+    part->staged_tab.reset();   // nor for stages
+    part->staged_refused = f->staged_refused;
     f->parts.emplace_back(part);
     f->part_k0.push_back(k0);
     f->part_trees.push_back(std::move(trees));
@@ -1823,6 +2004,7 @@ int ti_forest_create(const ti_forest_desc* desc, const int32_t* devices, int32_t
   keep_shap_source(desc, f.get());
   keep_approx_source(desc, f.get());
   keep_quantile_source(desc, f.get());
+  keep_staged_source(desc, f.get());
   keep_sparse_source(desc, f.get());
   if (desc->n_pre_steps > 0) {
     f->host->pre_op.assign(desc->pre_op, desc->pre_op + desc->n_pre_steps);
@@ -1898,6 +2080,25 @@ int ti_forest_set_quantiles(ti_forest* f, const double* q, int32_t n_q) {
     if (!(q[i] >= 0.0 && q[i] <= 1.0))
       return fail(TI_ERR_INVALID, "quantile level " + std::to_string(i) + " is outside [0, 1]");
   f->quant_q.assign(q, q + n_q);
+  return TI_OK;
+}
+
+int ti_forest_set_stages(ti_forest* f, int32_t begin, const int32_t* ends, int32_t n_stages,
+                         int32_t transformed) {
+  if (!f) return fail(TI_ERR_INVALID, "null forest");
+  if (!ends || n_stages < 1) return fail(TI_ERR_INVALID, "stages: need at least one end");
+  if (transformed != 0 && transformed != 1) return fail(TI_ERR_INVALID, "stages: transformed must be 0 or 1");
+  if (begin < 0) return fail(TI_ERR_INVALID, "stages: begin must be >= 0");
+  int32_t prev = begin;
+  for (int32_t i = 0; i < n_stages; ++i) {
+    if (ends[i] <= prev || ends[i] > f->T)
+      return fail(TI_ERR_INVALID, "stages: need begin < ends[0] < ends[1] < ... <= " + std::to_string(f->T) +
+                                      " trees, end " + std::to_string(i) + " is " + std::to_string(ends[i]));
+    prev = ends[i];
+  }
+  f->stage_begin = begin;
+  f->stage_transformed = transformed;
+  f->stage_ends.assign(ends, ends + n_stages);
   return TI_OK;
 }
 
@@ -1989,7 +2190,7 @@ int ti_forest_set_option(ti_forest* f, int32_t option, int64_t value) {
 int ti_output_shape(const ti_forest* f, int32_t kind, int64_t n_rows, int64_t* out_len,
                     int32_t* out_dtype) {
   if (!f || !out_len || !out_dtype) return fail(TI_ERR_INVALID, "null argument");
-  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_TREE_QUANTILE) return fail(TI_ERR_INVALID, "bad output kind");
+  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_STAGED) return fail(TI_ERR_INVALID, "bad output kind");
   if (n_rows < 0) return fail(TI_ERR_INVALID, "negative n_rows");
   *out_len = n_rows * output_width(f, kind);
   *out_dtype = output_dtype(f, kind);
@@ -2000,7 +2201,7 @@ static int check_call(const ti_forest* f, const void* X, int32_t xdt, int64_t ro
                       int64_t stride, int32_t kind, const void* out, int64_t out_len) {
   if (!f) return fail(TI_ERR_INVALID, "null forest");
   if (xdt != TI_F32 && xdt != TI_F64) return fail(TI_ERR_INVALID, "x_dtype must be TI_F32 or TI_F64");
-  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_TREE_QUANTILE) return fail(TI_ERR_INVALID, "bad output kind");
+  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_STAGED) return fail(TI_ERR_INVALID, "bad output kind");
   if (rows < 0) return fail(TI_ERR_INVALID, "negative n_rows");
   if (rows == 0) return TI_OK;
   if (!X || !out) return fail(TI_ERR_INVALID, "null data pointer");
@@ -2068,7 +2269,7 @@ int ti_predict_csr(ti_forest* f, const int64_t* indptr, const int32_t* indices, 
   if (xdt != TI_F32 && xdt != TI_F64) return fail(TI_ERR_INVALID, "x_dtype must be TI_F32 or TI_F64");
   if (absent != TI_CSR_ABSENT_ZERO && absent != TI_CSR_ABSENT_NAN)
     return fail(TI_ERR_INVALID, "absent must be TI_CSR_ABSENT_ZERO or TI_CSR_ABSENT_NAN");
-  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_TREE_QUANTILE) return fail(TI_ERR_INVALID, "bad output kind");
+  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_STAGED) return fail(TI_ERR_INVALID, "bad output kind");
   if (kind != TI_OUTPUT_MARGIN && kind != TI_OUTPUT_PREDICT && kind != TI_OUTPUT_LEAF)
     return fail(TI_ERR_UNSUPPORTED, "CSR rows serve TI_OUTPUT_MARGIN, TI_OUTPUT_PREDICT and "
                                     "TI_OUTPUT_LEAF; output kind " + std::to_string(kind) +

@@ -43,6 +43,7 @@ enum class Walk {
   SparseImage,      // CSR rows, the used columns in an LDS image  sparse_explicit_predict_kernel
   SparseSearch,     // CSR rows, each column searched in its row   (treeinfer_sparse.h)
   TreeLanes,        // small batches: a lane a tree, a workgroup a row  tree_lanes_predict_kernel
+  StagedAccum,      // TI_OUTPUT_STAGED's pass 2 over leaf ids   staged_accum_kernel
 };
 
 struct KernelKey {
@@ -55,6 +56,7 @@ struct KernelKey {
   int ilp;           // record walks and bottoms: trees a lane walks at once
   int prefetch;      // BinHeap: prefetch depth
   int groups;        // BinHeapFixed: groups of 4 trees a stage (NG)
+  bool vector_leaf;  // StagedAccum: a vector a leaf (else a scalar)
 };
 
 // A rule calls `f` with the template argument it chose, as an
@@ -153,6 +155,8 @@ KernelFn select_walk(const KernelKey& k) {
       break;   // kernels_sparse
     case Walk::TreeLanes:
       break;   // kernels_small
+    case Walk::StagedAccum:
+      break;   // kernels_staged
   }
   return nullptr;
 }
@@ -173,6 +177,7 @@ KernelFn kernels_crec(const KernelKey& k);  // the categorical records, every pa
 KernelFn kernels_obliv(const KernelKey& k); // the oblivious trees, every pair
 KernelFn kernels_sparse(const KernelKey& k);// the CSR walk, every pair
 KernelFn kernels_small(const KernelKey& k); // the small-batch walk, every pair
+KernelFn kernels_staged(const KernelKey& k);// the staged pass, both accumulators
 
 inline KernelFn select(const KernelKey& k) {
   if (k.walk == Walk::CatHeapXgb || k.walk == Walk::CatHeapLgb) return kernels_cat(k);
@@ -180,6 +185,7 @@ inline KernelFn select(const KernelKey& k) {
   if (k.walk == Walk::Oblivious || k.walk == Walk::ObliviousGather) return kernels_obliv(k);
   if (k.walk == Walk::SparseImage || k.walk == Walk::SparseSearch) return kernels_sparse(k);
   if (k.walk == Walk::TreeLanes) return kernels_small(k);
+  if (k.walk == Walk::StagedAccum) return kernels_staged(k);
   if (!k.x64) return k.acc64 ? kernels_fd(k) : kernels_ff(k);
   return k.acc64 ? kernels_dd(k) : kernels_df(k);
 }

@@ -312,6 +312,13 @@ struct QuantilePtrs {
   double* quant_weights = nullptr;      // [T]
 };
 
+// Staged-prediction tables (treeinfer.hip: ensure_staged).  A float64 forest
+// of one scalar output reads the tree-quantile tables instead and owns none.
+struct StagedPtrs {
+  int64_t* staged_leaf_base = nullptr;   // [T + 1] first leaf of each tree
+  void* staged_leaves = nullptr;         // per (tree, leaf id) leaf_width values, ACC-typed
+};
+
 // The sparse image of ti_predict_csr (treeinfer_sparse.h: ensure_sparse).  The
 // slot nodes, the used columns and slot_of_col are the image's own; ex is the
 // layout-1 set both regimes walk beside them: a layout-1 forest's resident
@@ -386,10 +393,10 @@ struct CallScratch {
 // tables (and the tree-quantile tables beside them), freed from the record of
 // what their uploads allocated (forest_mem / shap_mem / approx_mem / quant_mem), and the scratch buffers, which grow() reallocates and
 // free_scratch frees.
-struct DeviceForest : ForestPtrs, ShapPtrs, ApproxPtrs, QuantilePtrs, SparsePtrs, ScratchBufs {
+struct DeviceForest : ForestPtrs, ShapPtrs, ApproxPtrs, QuantilePtrs, StagedPtrs, SparsePtrs, ScratchBufs {
   int device = -1;
   hipStream_t stream = nullptr;
-  DeviceAllocs forest_mem, shap_mem, approx_mem, quant_mem, sparse_mem, ex_mem;
+  DeviceAllocs forest_mem, shap_mem, approx_mem, quant_mem, staged_mem, sparse_mem, ex_mem;
   std::atomic<int32_t> shap_tab_state{0};   // 0 not tried, 1 built, -1 failed or over the cap:
                                      // contributions use the extend / unwind kernel
   // TI_OUTPUT_INTERACT scratch (launch_interact: contributions + partials of
@@ -696,6 +703,22 @@ struct ti_forest {
   };
   std::unique_ptr<QuantileTables> quant_tab;
   std::vector<double> quant_q{0.5};
+  // Staged predictions (TI_OUTPUT_STAGED, treeinfer_staged.h): staged_refused
+  // names why the forest cannot serve them (empty: it can).  The leaf table is
+  // built at create and uploaded on the first call (ensure_staged, under
+  // shap_mu); staged_shared: the forest reads the tree-quantile tables, which
+  // hold the same float64 values, and keeps none of its own.  The stages are
+  // written by ti_forest_set_stages with no staged call in flight.
+  std::string staged_refused;
+  std::atomic<bool> staged_ready{false};
+  bool staged_shared = false;
+  struct StagedTables {
+    std::vector<int64_t> leaf_base;
+    std::vector<unsigned char> leaves;   // ACC-typed
+  };
+  std::unique_ptr<StagedTables> staged_tab;
+  int32_t stage_begin = 0, stage_transformed = 0;
+  std::vector<int32_t> stage_ends;   // fill_model sets the default: 0, {T}, 0
   // Interventional contributions (TI_OUTPUT_CONTRIB_INTERV): rows of the
   // background set by ti_forest_set_background, 0 for none.  Written with no
   // call in flight, so calls read it without a lock.

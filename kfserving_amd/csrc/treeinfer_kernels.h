@@ -146,6 +146,15 @@ struct KArgs {
   int32_t sp_U;
   int32_t sp_absent_nan;          // an entry not stored reads NaN (else +0.0)
   int64_t sp_node_last;           // last valid index of `nodes` / `thr64`
+  // staged accumulation (TI_OUTPUT_STAGED, treeinfer_staged.h), after them for
+  // the same reason.  `leaf_base` is then the [T + 1] table of the leaf ids and
+  // `leaves` the [.][leaf_width] values it addresses.
+  const int32_t* st_leaf_ids;     // [n_rows][T] pass 1's output for the rows of this launch
+  const int32_t* st_ends;         // [st_n] the stage ends, ascending
+  int32_t st_begin;               // first tree of the chain
+  int32_t st_n;                   // stages S
+  int32_t st_width;               // outputs a stage W
+  int32_t st_tile;                // elements a row of the LDS output tile holds
 };
 
 __device__ __forceinline__ size_t align16(size_t x) { return (x + 15) & ~size_t(15); }

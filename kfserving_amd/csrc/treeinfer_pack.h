@@ -136,6 +136,9 @@ void fill_model(const ti_forest_desc* desc, const std::vector<int>& depth, ti_fo
   f->transform = desc->transform;
   f->tparam = desc->transform_param;
   f->divisor = desc->average_divisor;
+  f->stage_begin = 0;   // TI_OUTPUT_STAGED's default: the whole forest's margin
+  f->stage_transformed = 0;
+  f->stage_ends.assign(1, desc->n_trees);
   if (f->K <= ti::kMaxGroups)
     for (int k = 0; k < f->K; ++k) f->base[k] = desc->base_margin[k];
   for (int64_t i = 0; i < desc->n_nodes; ++i)

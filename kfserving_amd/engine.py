@@ -19,9 +19,10 @@ from typing import Optional, Sequence
 import numpy as np
 
 from .forest import (Forest, OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_CONTRIB_INTERV, OUT_INTERACT,
-                     OUT_LEAF, OUT_MARGIN, OUT_PREDICT, OUT_TREE_QUANTILE, TI_F32, TI_F64, TI_I32)
+                     OUT_LEAF, OUT_MARGIN, OUT_PREDICT, OUT_STAGED, OUT_TREE_QUANTILE,
+                     TI_F32, TI_F64, TI_I32)
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 _LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("TREEINFER_LIB", os.path.join(_LIB_DIR, "libtreeinfer.so"))
 
@@ -30,6 +31,7 @@ EXPORTED_SYMBOLS = (
     "ti_predict", "ti_predict_device", "ti_transform_device", "ti_last_error", "ti_device_count",
     "ti_abi_version", "ti_forest_set_option", "ti_pretransform_device",
     "ti_forest_set_background", "ti_forest_set_quantiles", "ti_predict_csr",
+    "ti_forest_set_stages",
 )
 
 # ti_predict_csr: what an entry the matrix does not store reads as
@@ -169,6 +171,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.ti_forest_set_background.argtypes = [vp, vp, i32, i64, i32, i64]
         lib.ti_forest_set_quantiles.restype = ctypes.c_int
         lib.ti_forest_set_quantiles.argtypes = [vp, vp, i32]
+        lib.ti_forest_set_stages.restype = ctypes.c_int
+        lib.ti_forest_set_stages.argtypes = [vp, i32, vp, i32, i32]
         if lib.ti_abi_version() != ABI_VERSION:
             raise TreeInferError(-1, f"ABI mismatch: library {lib.ti_abi_version()}, "
                                      f"binding {ABI_VERSION}")
@@ -280,6 +284,8 @@ class DeviceForest:
                                                      ctypes.byref(handle)))
         self._handle = handle
         self.quantiles = (0.5,)     # this handle's OUT_TREE_QUANTILE levels (set_quantiles)
+        # this handle's OUT_STAGED stages (set_stages): begin, ends, transformed
+        self.stages = (0, (f.n_trees,), False)
 
     # ------------------------------------------------------------------ info
     def info(self) -> dict:
@@ -320,6 +326,25 @@ class DeviceForest:
                                                             int(levels.shape[0])))
         self.quantiles = tuple(float(v) for v in levels)
 
+    def set_stages(self, ends, begin: int = 0, transformed: bool = False) -> None:
+        """ti_forest_set_stages: OUT_STAGED then answers, for each ``e`` of
+        ``ends`` (tree counts, ascending, ``begin < e <= n_trees``), what the
+        trees ``[begin, e)`` alone give -- ``tree_subset(begin, e)``'s
+        OUT_MARGIN, or its OUT_PREDICT when ``transformed`` -- as
+        [rows, len(ends), W].  Call it with no predict in flight on this
+        forest."""
+        arr = np.ascontiguousarray(np.atleast_1d(np.asarray(ends)), dtype=np.int32)
+        if arr.ndim != 1:
+            raise ValueError(f"stage ends must be a flat list, got shape {arr.shape}")
+        _check(self._lib, self._lib.ti_forest_set_stages(self._handle, int(begin), _ptr(arr),
+                                                         int(arr.shape[0]), 1 if transformed else 0))
+        self.stages = (int(begin), tuple(int(v) for v in arr), bool(transformed))
+
+    def stage_width(self) -> int:
+        """Outputs of one OUT_STAGED stage: K, or OUT_PREDICT's width when
+        the stages are transformed."""
+        return self.forest.output_width(OUT_PREDICT if self.stages[2] else OUT_MARGIN)
+
     def linear_tile_rows(self, x_dtype) -> int:
         """Rows per tile of the linear-leaf pass (launch_linear in
         treeinfer.hip) for input of ``x_dtype``: the largest of 256 / 128 / 64
@@ -354,12 +379,17 @@ class DeviceForest:
             return self._predict_csr(X, kind, CSR_ABSENT[absent])
         X = self.prepare_input(X)
         rows, cols = X.shape
-        width = len(self.quantiles) if kind == OUT_TREE_QUANTILE else self.forest.output_width(kind)
+        if kind == OUT_STAGED:
+            width = len(self.stages[1]) * self.stage_width()
+        else:
+            width = len(self.quantiles) if kind == OUT_TREE_QUANTILE else self.forest.output_width(kind)
         out = np.empty(rows * width, dtype=self.forest.output_dtype(kind))
         xdt = TI_F32 if X.dtype == np.float32 else TI_F64
         if rows:
             _check(self._lib, self._lib.ti_predict(self._handle, _ptr(X), xdt, rows, cols, cols,
                                                    kind, _ptr(out), out.shape[0]))
+        if kind == OUT_STAGED:
+            return out.reshape(rows, len(self.stages[1]), self.stage_width())
         if width == 1 and kind != OUT_LEAF:
             return out
         return out.reshape(rows, width)
@@ -378,7 +408,9 @@ class DeviceForest:
         indices = np.ascontiguousarray(csr.indices, dtype=np.int32)
         data = np.ascontiguousarray(csr.data, dtype=np.float32 if csr.data.dtype == np.float32
                                     else np.float64)
-        width = self.forest.output_width(kind)
+        # the library refuses OUT_STAGED of CSR rows; it still gets a buffer of the kind's size
+        width = (len(self.stages[1]) * self.stage_width() if kind == OUT_STAGED
+                 else self.forest.output_width(kind))
         out = np.empty(rows * width, dtype=self.forest.output_dtype(kind))
         if rows:
             _check(self._lib, self._lib.ti_predict_csr(
@@ -447,5 +479,5 @@ __all__ = ["DeviceForest", "TreeInferError", "prepare_input", "load_library", "d
            "OPT_SHAP_TABLE_ROWS", "OPT_SHAP_TABLE_MB", "OPT_HOST_REGISTER", "OPT_LINEAR_SCRATCH_MB",
            "OPT_SMALL_BATCH_ROWS",
            "EXPORTED_SYMBOLS", "OUT_MARGIN", "OUT_PREDICT", "OUT_LEAF", "OUT_CONTRIB", "OUT_INTERACT",
-           "OUT_CONTRIB_APPROX", "OUT_CONTRIB_INTERV", "OUT_TREE_QUANTILE",
+           "OUT_CONTRIB_APPROX", "OUT_CONTRIB_INTERV", "OUT_TREE_QUANTILE", "OUT_STAGED",
            "TI_F32", "TI_F64", "TI_I32"]

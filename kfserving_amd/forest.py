@@ -49,6 +49,7 @@ OUT_INTERACT = 4    # SHAP interaction values [rows, K * (F + 1) * (F + 1)] (pre
 OUT_CONTRIB_APPROX = 5   # approximate (Saabas) contributions, laid out as OUT_CONTRIB (approx_contribs)
 OUT_CONTRIB_INTERV = 6   # interventional TreeSHAP against a background set, laid out as OUT_CONTRIB
 OUT_TREE_QUANTILE = 7    # weighted quantiles of a row's per-tree predictions [rows, n_q]
+OUT_STAGED = 8           # the margins or predictions after chosen numbers of trees [rows, S, W]
 TREE_QUANTILE_MAX_TREES = 4096     # the kernel's cap (treeinfer_quantile.h)
 TREE_QUANTILE_MAX_LEVELS = 8
 
@@ -336,6 +337,8 @@ class Forest:
             return self.n_groups * (self.n_features + 1) ** 2
         if kind == OUT_TREE_QUANTILE:   # as many as the device handle has levels
             raise ValueError("OUT_TREE_QUANTILE's width is DeviceForest.quantiles', not the forest's")
+        if kind == OUT_STAGED:          # as many as the device handle has stages
+            raise ValueError("OUT_STAGED's width is DeviceForest.stages', not the forest's")
         if kind == OUT_PREDICT and self.transform == T_ARGMAX:
             return 1
         return self.n_groups

@@ -264,7 +264,8 @@ def parse_lightgbm_text(text: str) -> Forest:
         average_divisor=float(n_iter) if average and n_iter > 0 else 1.0,
         transform=transform, transform_param=tparam, input_dtype=TI_F64,
         library="lightgbm", objective=objective, feature_names=names,
-        meta={"version": header.get("version", ""), "num_class": int(header.get("num_class", 1))},
+        meta={"version": header.get("version", ""), "num_class": int(header.get("num_class", 1)),
+              "trees_per_iteration": ntpi},
         cat_bits=cat_bits, cat_offset=cat_offset, cat_nwords=cat_nwords,
         lin_offset=lin_offset, lin_feature=lin_feature, lin_coeff=lin_coeff, lin_const=lin_const,
     ).contiguous()

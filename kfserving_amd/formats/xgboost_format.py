@@ -203,8 +203,11 @@ def _concat_categories(trees: List[dict]):
 
 def _assemble(trees: List[dict], tree_info: np.ndarray, num_feature: int, num_group: int,
               base_score, objective: str, base_is_margin: bool, base_first: bool,
-              version: Tuple[int, int, int], feature_names=None, fmt: str = "") -> Forest:
-    """``base_score``: one value, or one per output group (xgboost >= 2 vector)."""
+              version: Tuple[int, int, int], feature_names=None, fmt: str = "",
+              num_parallel_tree=1) -> Forest:
+    """``base_score``: one value, or one per output group (xgboost >= 2 vector).
+    ``num_parallel_tree``: trees a group gets each boosting iteration, None
+    where the model file does not say."""
     cat = concat_trees(trees, 1)
     cat_bits, cat_offset, cat_nwords = _concat_categories(trees)
     used = cat["feature"][cat["feature"] >= 0]
@@ -231,9 +234,30 @@ def _assemble(trees: List[dict], tree_info: np.ndarray, num_feature: int, num_gr
         transform=objective_transform(objective), transform_param=1.0,
         input_dtype=TI_F32, library="xgboost", objective=objective,
         feature_names=feature_names,
-        meta={"format": fmt, "version": version, "base_score": base_score},
+        # trees a boosting iteration adds: num_parallel_tree a group; None where
+        # the file does not say (xgbserver then refuses "iteration_range")
+        meta={"format": fmt, "version": version, "base_score": base_score,
+              "trees_per_iteration": (None if num_parallel_tree is None
+                                      else K * int(num_parallel_tree))},
         cat_bits=cat_bits, cat_offset=cat_offset, cat_nwords=cat_nwords,
     ).contiguous()
+
+
+def _binary_parallel_trees(field: int, tree_info: np.ndarray, num_group: int):
+    """num_parallel_tree of a binary model, or None.  The header's second
+    field is num_roots (always 1) in xgboost 0.82 and num_parallel_tree in the
+    releases that renamed it; 0.82 kept num_parallel_tree in the training
+    parameters alone.  So a value above 1 is the count.  Otherwise a multiclass
+    model shows it: an iteration's trees are stored group by group, so the run
+    of trees of the first group at the start of tree_info is one group's
+    share.  A single-group model whose field is 1 does not say."""
+    if field > 1:
+        return int(field)
+    ti = np.asarray(tree_info)
+    if num_group > 1 and ti.size:
+        change = np.nonzero(ti != ti[0])[0]
+        return int(change[0]) if change.size else None
+    return None
 
 
 def _parse_binary(buf: bytes, pos: int, fmt: str) -> Forest:
@@ -284,7 +308,8 @@ def _parse_binary(buf: bytes, pos: int, fmt: str) -> Forest:
     # xgboost >= 1.0 deprecates num_output_group in favour of the learner's num_class
     num_group = max(1, num_output_group, num_class)
     f = _assemble(trees, tree_info, num_feature, num_group, base_score, objective,
-                  base_is_margin=base_is_margin, base_first=False, version=version, fmt=fmt)
+                  base_is_margin=base_is_margin, base_first=False, version=version, fmt=fmt,
+                  num_parallel_tree=_binary_parallel_trees(num_roots, tree_info, num_group))
     f.meta["attributes"] = attrs
     f.meta["trailing_bytes"] = len(buf) - r.pos
     return f
@@ -394,9 +419,10 @@ def _parse_json(doc: dict) -> Forest:
         trees.append(t)
     K = max(1, num_class)
     names = learner.get("feature_names") or None
+    npt = max(1, int(_json_num(model.get("gbtree_model_param", {}).get("num_parallel_tree", 1))))
     return _assemble(trees, model["tree_info"], num_feature, K, base_score, objective,
                      base_is_margin=False, base_first=version >= (1, 4, 0), version=version,
-                     feature_names=names, fmt="json")
+                     feature_names=names, fmt="json", num_parallel_tree=npt)
 
 
 def parse_xgboost_bytes(buf: bytes) -> Forest:

@@ -20,6 +20,10 @@ BOOSTER_FILE = "model.bst"
 
 
 class LightGBMModel(GPUForestMixin, KFModel):
+    # request keys beside "inputs" that change the answer: KFServer sends such
+    # a request to predict() alone, never through a batcher
+    unbatched_request_keys = ("start_iteration", "num_iteration")
+
     def __init__(self, name: str, model_dir: str, nthread: int, booster: Forest = None,
                  background=None):
         super().__init__(name)
@@ -56,9 +60,33 @@ class LightGBMModel(GPUForestMixin, KFModel):
                              "in training data (%d)." % (X.shape[-1], n))
         return X
 
+    def iteration_trees(self, request: Dict):
+        """The request's optional ``"start_iteration"`` / ``"num_iteration"``
+        keys (LightGBM's own: num_iteration <= 0 or absent means every iteration
+        from the start on) as a tree range; None when both are absent.  An
+        iteration is num_tree_per_iteration trees."""
+        if not isinstance(request, dict) or not any(k in request for k in self.unbatched_request_keys):
+            return None
+        f = self._forest
+        per = int(f.meta.get("trees_per_iteration", f.n_groups))
+        b, n = request.get("start_iteration", 0), request.get("num_iteration", -1)
+        n = -1 if n is None else n
+        if not all(isinstance(v, int) and not isinstance(v, bool) for v in (b, n)):
+            raise ValueError('"start_iteration" and "num_iteration" must be integers')
+        n_iter = f.n_trees // per
+        b = max(b, 0)
+        e = n_iter if n <= 0 else min(b + n, n_iter)
+        if not b < e:
+            raise ValueError('"start_iteration" %d is beyond the model\'s %d iterations' % (b, n_iter))
+        return b * per, e * per
+
     def predict(self, request: Dict) -> Dict:
         try:
-            result = self.predict_matrix(self.request_matrix(request))
+            trees = self.iteration_trees(request)
+            X = self.request_matrix(request)
+            if trees is not None:
+                return {"predictions": self.predict_tree_range(X, *trees).tolist()}
+            result = self.predict_matrix(X)
             return {"predictions": result.tolist()}
         except Exception as e:
             raise Exception("Failed to predict %s" % e)

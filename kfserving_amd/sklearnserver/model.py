@@ -30,7 +30,7 @@ ARRAYS_EXTENSION = ".npz"
 class SKLearnModel(GPUForestMixin, KFModel):  # pylint:disable=c-extension-no-member
     # request keys beside "instances" that change the answer: KFServer sends
     # such a request to predict() alone, never through a batcher
-    unbatched_request_keys = ("quantiles",)
+    unbatched_request_keys = ("quantiles", "stages")
 
     def __init__(self, name: str, model_dir: str, background=None):
         super().__init__(name)
@@ -251,6 +251,30 @@ class SKLearnModel(GPUForestMixin, KFModel):  # pylint:disable=c-extension-no-me
                              % TREE_QUANTILE_MAX_LEVELS)
         return q
 
+    def stage_ends(self, request: Dict):
+        """The request's optional ``"stages": [n, ...]`` key, checked, as tree
+        counts: None when absent.  Served for GradientBoosting and
+        HistGradientBoosting models; stage n is what ``staged_predict`` yields
+        at iteration n (1 .. n_estimators), an iteration being one tree a
+        class."""
+        if not isinstance(request, dict) or "stages" not in request:
+            return None
+        if "quantiles" in request:
+            raise ValueError('"stages" and "quantiles" together are not served')
+        f = self._forest
+        if not (f.objective.startswith("GradientBoosting")
+                or f.objective.startswith("HistGradientBoosting")):
+            raise ValueError('"stages" is served for GradientBoosting and HistGradientBoosting '
+                             "models, not for this %s" % (f.objective or "model"))
+        per = f.n_groups if f.leaf_width == 1 else 1
+        n_iter = f.n_trees // per
+        st = request["stages"]
+        if (not isinstance(st, (list, tuple)) or not st
+                or not all(isinstance(v, int) and not isinstance(v, bool) for v in st)
+                or any(b <= a for a, b in zip(st, st[1:])) or st[0] < 1 or st[-1] > n_iter):
+            raise ValueError('"stages" must be a list of ascending iterations in 1 .. %d' % n_iter)
+        return [n * per for n in st]
+
     def native_v1_labels(self):
         """A classifier's labels as its predict renders them
         (classes.take(index).tolist() -> json.dumps), for the native route."""
@@ -275,8 +299,16 @@ class SKLearnModel(GPUForestMixin, KFModel):  # pylint:disable=c-extension-no-me
         inputs = self._array(request)
         try:
             f = self._forest
+            ends = self.stage_ends(request)     # first: it refuses the two keys together
             levels = self.quantile_levels(request)
             X = self.request_matrix({"instances": inputs})
+            if ends is not None:        # predictions[row][s], as staged_predict yields them
+                result = self.predict_stages(X, ends)
+                result = result[:, :, 0] if result.shape[2] == 1 else result
+                classes = f.meta.get("classes")
+                if classes is not None:     # a classifier's stage is a label index, W = 1
+                    result = np.asarray(classes).take(result.astype(np.int64), axis=0)
+                return {"predictions": result.tolist()}
             if levels is not None:      # [rows][n_q], one level included
                 result = self.predict_quantiles(X, levels).reshape(X.shape[0], levels.shape[0])
                 return {"predictions": result.tolist()}

@@ -17,7 +17,7 @@ import numpy as np
 
 from .engine import DeviceForest, prepare_input
 from .forest import (OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_CONTRIB_INTERV, OUT_INTERACT, OUT_PREDICT,
-                     OUT_TREE_QUANTILE, Forest)
+                     OUT_STAGED, OUT_TREE_QUANTILE, Forest)
 
 BACKGROUND_FILE = "background.npy"
 
@@ -92,6 +92,28 @@ class GPUForestMixin:
             if dev.quantiles != tuple(float(v) for v in levels):
                 dev.set_quantiles(levels)
             return dev.predict(X, OUT_TREE_QUANTILE)
+
+    def predict_stages(self, X: np.ndarray, ends, begin: int = 0,
+                       transformed: bool = True) -> np.ndarray:
+        """OUT_STAGED: what the trees [begin, e) give for each e of ``ends``,
+        [rows, len(ends), W].  The stages are the device forest's own state, so
+        every staged call of a model takes one lock around setting them and
+        predicting, as the quantile calls do."""
+        dev = self.device_forest()
+        want = (int(begin), tuple(int(e) for e in ends), bool(transformed))
+        with self._dev_lock:
+            if dev.stages != want:
+                dev.set_stages(want[1], begin=want[0], transformed=want[2])
+            return dev.predict(X, OUT_STAGED)
+
+    def predict_tree_range(self, X: np.ndarray, begin: int, end: int) -> np.ndarray:
+        """The model's prediction from the trees [begin, end) alone, shaped
+        as predict_matrix shapes the whole model's."""
+        T = self._forest.n_trees
+        if not 0 <= begin < end <= T:
+            raise ValueError("trees [%d, %d) are no range of the model's %d trees" % (begin, end, T))
+        out = self.predict_stages(X, (end,), begin=begin)[:, 0, :]
+        return out[:, 0] if out.shape[1] == 1 else out
 
     # V2 tensors (kfserving.v2): a [rows, features] numeric matrix, read with
     # the numpy-argument semantics of each library (NaN = missing)

@@ -31,7 +31,7 @@ from typing import Callable, List, Optional, Tuple
 import numpy as np
 
 from .forest import (OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_CONTRIB_INTERV, OUT_INTERACT, OUT_LEAF, OUT_MARGIN, OUT_PREDICT,
-                     OUT_TREE_QUANTILE, TI_F32, Forest)
+                     OUT_STAGED, OUT_TREE_QUANTILE, TI_F32, Forest)
 
 
 def partition_trees(forest: Forest, world: int) -> List[Tuple[int, int]]:
@@ -95,7 +95,7 @@ class TreeShardedForest:
         same rows).  Returns the full output on the root (PREDICT and LEAF
         shaped as DeviceForest.predict returns them, MARGIN [rows, K], CONTRIB
         and CONTRIB_APPROX [rows, K * (F + 1)]) and None elsewhere.
-        OUT_INTERACT, OUT_CONTRIB_INTERV and OUT_TREE_QUANTILE are not served
+        OUT_INTERACT, OUT_CONTRIB_INTERV, OUT_TREE_QUANTILE and OUT_STAGED are not served
         tree-sharded: each raises ValueError."""
         if kind == OUT_INTERACT:   # it would fall through to the margin path below
             raise ValueError("kind OUT_INTERACT (SHAP interaction values) is not served "
@@ -103,6 +103,8 @@ class TreeShardedForest:
         if kind == OUT_TREE_QUANTILE:    # an order statistic over all trees: no sum of shards
             raise ValueError("kind OUT_TREE_QUANTILE (quantiles across trees) is not served "
                              "tree-sharded; use DeviceForest.predict")
+        if kind == OUT_STAGED:           # a stage end cuts the shards unevenly: not served here
+            raise ValueError("kind OUT_STAGED (staged predictions) is not served tree-sharded")
         if kind == OUT_CONTRIB_INTERV:   # no rank's engine holds a background
             raise ValueError("kind OUT_CONTRIB_INTERV (interventional contributions) is not "
                              "served tree-sharded; use DeviceForest.predict")

@@ -21,6 +21,10 @@ BOOSTER_FILE = "model.bst"
 
 
 class XGBoostModel(GPUForestMixin, KFModel):
+    # a request key beside "instances" that changes the answer: KFServer sends
+    # such a request to predict() alone, never through a batcher
+    unbatched_request_keys = ("iteration_range",)
+
     def __init__(self, name: str, model_dir: str, nthread: int, booster: Forest = None,
                  background=None):
         super().__init__(name)
@@ -85,9 +89,41 @@ class XGBoostModel(GPUForestMixin, KFModel):
             return np.asarray(chunk), 1
         return super().native_request(chunk, kind)
 
+    def iteration_trees(self, request: Dict):
+        """The request's optional ``"iteration_range": [begin, end]`` key
+        (xgboost's own: boosting iterations, end 0 meaning all of them) as a
+        tree range; None when absent.  An iteration is
+        ``meta["trees_per_iteration"]`` trees (n_groups x num_parallel_tree);
+        a model file that does not say how many refuses the key.  The model's best_iteration is
+        not applied when the key is absent."""
+        if not isinstance(request, dict) or "iteration_range" not in request:
+            return None
+        f = self._forest
+        per = f.meta.get("trees_per_iteration")
+        if per is None:
+            raise ValueError('"iteration_range" needs the trees of an iteration, which this model '
+                             "file does not record (a one-group legacy binary model): save it as "
+                             "JSON or UBJSON")
+        rng = request["iteration_range"]
+        if (not isinstance(rng, (list, tuple)) or len(rng) != 2
+                or not all(isinstance(v, int) and not isinstance(v, bool) for v in rng)):
+            raise ValueError('"iteration_range" must be [begin, end], two integers')
+        n_iter = f.n_trees // int(per)
+        per = int(per)
+        b, e = rng
+        e = n_iter if e == 0 else e
+        if not 0 <= b < e <= n_iter:
+            raise ValueError('"iteration_range" [%d, %d) is outside the model\'s %d iterations'
+                             % (b, e, n_iter))
+        return b * per, e * per
+
     def predict(self, request: Dict) -> Dict:
         try:
-            result = self.predict_matrix(self.request_matrix(request))
+            trees = self.iteration_trees(request)
+            X = self.request_matrix(request)
+            if trees is not None:
+                return {"predictions": self.predict_tree_range(X, *trees).tolist()}
+            result = self.predict_matrix(X)
             return {"predictions": result.tolist()}
         except Exception as e:
             raise Exception("Failed to predict %s" % e)
