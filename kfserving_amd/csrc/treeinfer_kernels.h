@@ -846,16 +846,93 @@ __device__ __forceinline__ void rank_search(const KArgs& a, const XT (&x)[Q], in
   }
 }
 
+// k = k5 + 1 + #{keys of e below x} as a carry chain: per key a compare and
+// an add with carry, no v_cndmask and no separate + 1.  (A NaN x compares
+// false four times, as `e < x` does.)  SE: the keys are uniform (SGPRs).
+template <bool SE>
+__device__ __forceinline__ uint32_t kary_count(float ex, float ey, float ez, float ew, float x,
+                                               uint32_t k5) {
+  uint32_t k;
+  if (SE)
+    asm("v_cmp_lt_f32 vcc, %1, %5\n\t"
+        "v_addc_co_u32 %0, vcc, 1, %6, vcc\n\t"
+        "v_cmp_lt_f32 vcc, %2, %5\n\t"
+        "v_addc_co_u32 %0, vcc, 0, %0, vcc\n\t"
+        "v_cmp_lt_f32 vcc, %3, %5\n\t"
+        "v_addc_co_u32 %0, vcc, 0, %0, vcc\n\t"
+        "v_cmp_lt_f32 vcc, %4, %5\n\t"
+        "v_addc_co_u32 %0, vcc, 0, %0, vcc"
+        : "=&v"(k) : "s"(ex), "s"(ey), "s"(ez), "s"(ew), "v"(x), "v"(k5) : "vcc");
+  else
+    asm("v_cmp_lt_f32 vcc, %1, %5\n\t"
+        "v_addc_co_u32 %0, vcc, 1, %6, vcc\n\t"
+        "v_cmp_lt_f32 vcc, %2, %5\n\t"
+        "v_addc_co_u32 %0, vcc, 0, %0, vcc\n\t"
+        "v_cmp_lt_f32 vcc, %3, %5\n\t"
+        "v_addc_co_u32 %0, vcc, 0, %0, vcc\n\t"
+        "v_cmp_lt_f32 vcc, %4, %5\n\t"
+        "v_addc_co_u32 %0, vcc, 0, %0, vcc"
+        : "=&v"(k) : "v"(ex), "v"(ey), "v"(ez), "v"(ew), "v"(x), "v"(k5) : "vcc");
+  return k;
+}
+
+// rank_search's 5-ary form for stage_bins' register path (float32 rows, the
+// features f0 .. f0 + Q - 1 all below F), the same ranks from fewer VALU:
+//  * the first level from scalar loads: node 0 of a feature is the same for
+//    every lane, so its 4 keys come by s_load_dwordx4 and the compares take
+//    them as SGPR sources: no gather and no address;
+//  * the other levels' gathers through a buffer resource over the tables
+//    (F nn 16 bytes, which bounds every read), the feature's table as the
+//    scalar offset and 16 k as the lane's 32-bit offset: no 64-bit address;
+//  * the count as a carry chain (kary_count).
+template <int Q>
+__device__ __forceinline__ void rank_search_kary_regs(const KArgs& a, const float (&x)[Q], int f0,
+                                                      uint32_t (&b)[Q]) {
+  typedef float f4_t __attribute__((ext_vector_type(4)));
+  typedef const __attribute__((address_space(4))) f4_t cf4_t;
+  const uint32_t nn = (kpow5(a.bin_kary) - 1u) / 4u;   // nodes per feature
+  const uint32_t bytes = (uint32_t)a.n_features * nn * 16u;
+  const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<void*>(a.bin_tbl), 0, (int)bytes, 0x00020000);
+  cf4_t* ts = reinterpret_cast<cf4_t*>(reinterpret_cast<uintptr_t>(a.bin_tbl));
+  uint32_t fb[Q], k[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    fb[q] = (uint32_t)(f0 + q) * nn;   // uniform
+    const f4_t e = ts[fb[q]];
+    k[q] = kary_count<true>(e.x, e.y, e.z, e.w, x[q], 0u);
+  }
+  for (int s = 1; s < a.bin_kary; ++s) {
+    u32x4 e[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) e[q] = __builtin_amdgcn_raw_buffer_load_b128(rt, k[q] * 16u, fb[q] * 16u, 0);
+#pragma unroll
+    for (int q = 0; q < Q; ++q)
+      k[q] = kary_count<false>(__uint_as_float(e[q].x), __uint_as_float(e[q].y), __uint_as_float(e[q].z),
+                               __uint_as_float(e[q].w), x[q], 5u * k[q]);
+  }
+#pragma unroll
+  for (int q = 0; q < Q; ++q) b[q] = 1u + k[q] - nn;
+}
+
 // Rank the lane's values x[0 .. Q) of features f .. f + Q - 1 (the first n of
 // them live) and store the packed bin words of row `tid` in the bin image.
-// Returns whether a live value is a NaN.
-template <typename XT, bool B16, int Q>
+// Returns whether a live value is a NaN.  TRIM (stage_bins' register path:
+// float32 rows, all Q features live): the 5-ary search in its trimmed form.
+template <typename XT, bool B16, int Q, bool TRIM = false>
 __device__ __forceinline__ bool bin_commit(const KArgs& a, const XT (&x)[Q], int f, int n, int R,
                                            int tid) {
   using BT = BinTraits<B16>;
   constexpr int P = BT::P;
   uint32_t b[Q];
-  rank_search<XT, Q>(a, x, f, b);
+  bool trimmed = false;
+  if constexpr (TRIM && sizeof(XT) == 4) {
+    // (the tables within a buffer resource's 2 GB: any forest of the fixed walk)
+    trimmed = a.bin_nb <= 0 && a.bin_kary > 0 &&
+              (uint64_t)a.n_features * ((kpow5(a.bin_kary) - 1u) / 4u) * 16u <= 0x7fffffffu;
+    if (trimmed) rank_search_kary_regs<Q>(a, x, f, b);
+  }
+  if (!trimmed) rank_search<XT, Q>(a, x, f, b);
   uint32_t w[Q / P];
   bool has_nan = false;
 #pragma unroll
@@ -885,14 +962,17 @@ __device__ __forceinline__ bool bin_commit(const KArgs& a, const XT (&x)[Q], int
 //    own row, the next segment's load in flight during this one's search.
 //    Compiled in with REGS only: the fixed kernels of at most 4 output groups
 //    (42-44 VGPRs, 92-98 SGPRs, 8 waves per SIMD with it; the 16-group ones
-//    sit at 64 VGPRs, and its scalars took them to 106 SGPRs and 7 waves);
+//    sit at 64 VGPRs, and its scalars took them to 106 SGPRs and 7 waves).
+//    With TRIM (the one-group kernel at 4 trees a stage, whose two-buffer
+//    launch is held to 6 waves per SIMD by its LDS) the 5-ary search runs in
+//    its trimmed form (rank_search_kary_regs: 100 SGPRs, 7 waves);
 //  * through `temp` (the tree-stage area, free at this point) bin_chunk
 //    columns at a time: a coalesced copy into [c][R], then every lane searches
 //    its own row's values (rank_search), Q features at once for Q independent
 //    load chains.
 // Returns (uniformly) whether a live row of the tile holds a NaN.  Ends in a
 // barrier.
-template <typename XT, bool B16, int Q = TI_BIN_Q, bool REGS = false>
+template <typename XT, bool B16, int Q = TI_BIN_Q, bool REGS = false, bool TRIM = false>
 __device__ __forceinline__ bool stage_bins(volatile int* flag, XT* temp, const KArgs& a,
                                            int64_t row0, int R, int tid) {
   using BT = BinTraits<B16>;
@@ -925,7 +1005,7 @@ __device__ __forceinline__ bool stage_bins(volatile int* flag, XT* temp, const K
 #pragma unroll
         for (int q = 0; q < Q; ++q) x[q] = zero_map(nx[q], a.lgb_zero_map);
         if (f0 + V < F) nx = *reinterpret_cast<const xv_t*>(xr + f0 + V);
-        has_nan |= bin_commit<XT, B16, Q>(a, x, f0, V, R, tid);
+        has_nan |= bin_commit<XT, B16, Q, TRIM>(a, x, f0, V, R, tid);
       }
       if (has_nan && tid < rows_here) *flag = 1;
       __syncthreads();
@@ -1365,7 +1445,7 @@ __global__ void __launch_bounds__(512) bheap_fix_kernel(const KArgs a) {
       pf[u] = src[i < n16_all ? i : n16_all - 1];
     }
   }
-  const bool tile_nan = stage_bins<XT, B16, 4 * NG, (KMAX <= 4)>(
+  const bool tile_nan = stage_bins<XT, B16, 4 * NG, (KMAX <= 4), (KMAX == 1 && NG == 1)>(
       flag, reinterpret_cast<XT*>(smem + kFixStage), a, row0, R, tid);
   float acc[KMAX];
   init_acc(acc, a);

@@ -92,6 +92,19 @@ __global__ void __launch_bounds__(256) k(unsigned* out, unsigned long long* stam
         asm volatile("global_load_dwordx2 %0, %1, %2" : "+v"(ld) : "v"(zero), "s"(stamps) : "memory");
         asm volatile("v_add_u32 %0, %0, %18\n\tv_add_u32 %1, %1, %18\n\tv_add_u32 %2, %2, %18\n\tv_add_u32 %3, %3, %18\n\tv_add_u32 %4, %4, %18\n\tv_add_u32 %5, %5, %18\n\tv_add_u32 %6, %6, %18\n\tv_add_u32 %7, %7, %18" ROUND_OPERANDS);
       }
+      // the forms that pay for a step constant with a VGPR (%18, %20, %8, %9: VGPR sources)
+      if (OP == 32) asm volatile("v_and_b32 %0, %18, %0\n\tv_and_b32 %1, %18, %1\n\tv_and_b32 %2, %18, %2\n\tv_and_b32 %3, %18, %3\n\tv_and_b32 %4, %18, %4\n\tv_and_b32 %5, %18, %5\n\tv_and_b32 %6, %18, %6\n\tv_and_b32 %7, %18, %7" ROUND_OPERANDS);
+      if (OP == 33) asm volatile("v_and_or_b32 %0, %0, %18, %20\n\tv_and_or_b32 %1, %1, %18, %20\n\tv_and_or_b32 %2, %2, %18, %20\n\tv_and_or_b32 %3, %3, %18, %20\n\tv_and_or_b32 %4, %4, %18, %20\n\tv_and_or_b32 %5, %5, %18, %20\n\tv_and_or_b32 %6, %6, %18, %20\n\tv_and_or_b32 %7, %7, %18, %20" ROUND_OPERANDS);
+      if (OP == 34) asm volatile("v_and_b32 %0, %18, %0\n\tv_or_b32 %0, %20, %0\n\tv_and_b32 %1, %18, %1\n\tv_or_b32 %1, %20, %1\n\tv_and_b32 %2, %18, %2\n\tv_or_b32 %2, %20, %2\n\tv_and_b32 %3, %18, %3\n\tv_or_b32 %3, %20, %3\n\tv_and_b32 %4, %18, %4\n\tv_or_b32 %4, %20, %4\n\tv_and_b32 %5, %18, %5\n\tv_or_b32 %5, %20, %5\n\tv_and_b32 %6, %18, %6\n\tv_or_b32 %6, %20, %6\n\tv_and_b32 %7, %18, %7\n\tv_or_b32 %7, %20, %7" ROUND_OPERANDS);
+      // the fixed step with both masks in VGPRs (against row 18's SGPR mask and literal)
+      if (OP == 35) asm volatile("v_and_or_b32 %16, %0, %8, %20\n\tv_and_b32 %16, %9, %0\n\tv_cmp_lt_u32_sdwa vcc, %0, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cndmask_b32 %0, %0, %18, vcc\n\tv_and_or_b32 %16, %1, %8, %20\n\tv_and_b32 %16, %9, %1\n\tv_cmp_lt_u32_sdwa vcc, %1, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cndmask_b32 %1, %1, %18, vcc\n\tv_and_or_b32 %16, %2, %8, %20\n\tv_and_b32 %16, %9, %2\n\tv_cmp_lt_u32_sdwa vcc, %2, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cndmask_b32 %2, %2, %18, vcc\n\tv_and_or_b32 %16, %3, %8, %20\n\tv_and_b32 %16, %9, %3\n\tv_cmp_lt_u32_sdwa vcc, %3, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cndmask_b32 %3, %3, %18, vcc\n\tv_and_or_b32 %16, %4, %8, %20\n\tv_and_b32 %16, %9, %4\n\tv_cmp_lt_u32_sdwa vcc, %4, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cndmask_b32 %4, %4, %18, vcc\n\tv_and_or_b32 %16, %5, %8, %20\n\tv_and_b32 %16, %9, %5\n\tv_cmp_lt_u32_sdwa vcc, %5, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cndmask_b32 %5, %5, %18, vcc\n\tv_and_or_b32 %16, %6, %8, %20\n\tv_and_b32 %16, %9, %6\n\tv_cmp_lt_u32_sdwa vcc, %6, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cndmask_b32 %6, %6, %18, vcc\n\tv_and_or_b32 %16, %7, %8, %20\n\tv_and_b32 %16, %9, %7\n\tv_cmp_lt_u32_sdwa vcc, %7, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cndmask_b32 %7, %7, %18, vcc" ROUND_OPERANDS);
+      // the arithmetic level 0 with its two address ops as issued, and with the two masks in VGPRs
+      // (rank, L and L ^ R stay SGPRs)
+      if (OP == 36) asm volatile("v_sub_u32 %0, %19, %18\n\tv_ashrrev_i32 %0, 31, %0\n\tv_and_b32 %0, %19, %0\n\tv_xor_b32 %0, %19, %0\n\tv_and_or_b32 %16, %0, %19, %20\n\tv_and_b32 %16, 0x7f8, %0\n\tv_sub_u32 %1, %19, %18\n\tv_ashrrev_i32 %1, 31, %1\n\tv_and_b32 %1, %19, %1\n\tv_xor_b32 %1, %19, %1\n\tv_and_or_b32 %16, %1, %19, %20\n\tv_and_b32 %16, 0x7f8, %1\n\tv_sub_u32 %2, %19, %18\n\tv_ashrrev_i32 %2, 31, %2\n\tv_and_b32 %2, %19, %2\n\tv_xor_b32 %2, %19, %2\n\tv_and_or_b32 %16, %2, %19, %20\n\tv_and_b32 %16, 0x7f8, %2\n\tv_sub_u32 %3, %19, %18\n\tv_ashrrev_i32 %3, 31, %3\n\tv_and_b32 %3, %19, %3\n\tv_xor_b32 %3, %19, %3\n\tv_and_or_b32 %16, %3, %19, %20\n\tv_and_b32 %16, 0x7f8, %3\n\tv_sub_u32 %4, %19, %18\n\tv_ashrrev_i32 %4, 31, %4\n\tv_and_b32 %4, %19, %4\n\tv_xor_b32 %4, %19, %4\n\tv_and_or_b32 %16, %4, %19, %20\n\tv_and_b32 %16, 0x7f8, %4\n\tv_sub_u32 %5, %19, %18\n\tv_ashrrev_i32 %5, 31, %5\n\tv_and_b32 %5, %19, %5\n\tv_xor_b32 %5, %19, %5\n\tv_and_or_b32 %16, %5, %19, %20\n\tv_and_b32 %16, 0x7f8, %5\n\tv_sub_u32 %6, %19, %18\n\tv_ashrrev_i32 %6, 31, %6\n\tv_and_b32 %6, %19, %6\n\tv_xor_b32 %6, %19, %6\n\tv_and_or_b32 %16, %6, %19, %20\n\tv_and_b32 %16, 0x7f8, %6\n\tv_sub_u32 %7, %19, %18\n\tv_ashrrev_i32 %7, 31, %7\n\tv_and_b32 %7, %19, %7\n\tv_xor_b32 %7, %19, %7\n\tv_and_or_b32 %16, %7, %19, %20\n\tv_and_b32 %16, 0x7f8, %7" ROUND_OPERANDS);
+      if (OP == 37) asm volatile("v_sub_u32 %0, %19, %18\n\tv_ashrrev_i32 %0, 31, %0\n\tv_and_b32 %0, %19, %0\n\tv_xor_b32 %0, %19, %0\n\tv_and_or_b32 %16, %0, %8, %20\n\tv_and_b32 %16, %9, %0\n\tv_sub_u32 %1, %19, %18\n\tv_ashrrev_i32 %1, 31, %1\n\tv_and_b32 %1, %19, %1\n\tv_xor_b32 %1, %19, %1\n\tv_and_or_b32 %16, %1, %8, %20\n\tv_and_b32 %16, %9, %1\n\tv_sub_u32 %2, %19, %18\n\tv_ashrrev_i32 %2, 31, %2\n\tv_and_b32 %2, %19, %2\n\tv_xor_b32 %2, %19, %2\n\tv_and_or_b32 %16, %2, %8, %20\n\tv_and_b32 %16, %9, %2\n\tv_sub_u32 %3, %19, %18\n\tv_ashrrev_i32 %3, 31, %3\n\tv_and_b32 %3, %19, %3\n\tv_xor_b32 %3, %19, %3\n\tv_and_or_b32 %16, %3, %8, %20\n\tv_and_b32 %16, %9, %3\n\tv_sub_u32 %4, %19, %18\n\tv_ashrrev_i32 %4, 31, %4\n\tv_and_b32 %4, %19, %4\n\tv_xor_b32 %4, %19, %4\n\tv_and_or_b32 %16, %4, %8, %20\n\tv_and_b32 %16, %9, %4\n\tv_sub_u32 %5, %19, %18\n\tv_ashrrev_i32 %5, 31, %5\n\tv_and_b32 %5, %19, %5\n\tv_xor_b32 %5, %19, %5\n\tv_and_or_b32 %16, %5, %8, %20\n\tv_and_b32 %16, %9, %5\n\tv_sub_u32 %6, %19, %18\n\tv_ashrrev_i32 %6, 31, %6\n\tv_and_b32 %6, %19, %6\n\tv_xor_b32 %6, %19, %6\n\tv_and_or_b32 %16, %6, %8, %20\n\tv_and_b32 %16, %9, %6\n\tv_sub_u32 %7, %19, %18\n\tv_ashrrev_i32 %7, 31, %7\n\tv_and_b32 %7, %19, %7\n\tv_xor_b32 %7, %19, %7\n\tv_and_or_b32 %16, %7, %8, %20\n\tv_and_b32 %16, %9, %7" ROUND_OPERANDS);
+      // the NaN step's VALU with the masks in VGPRs, and as issued (row 18's forms)
+      if (OP == 38) asm volatile("v_and_or_b32 %16, %0, %8, %20\n\tv_and_b32 %16, %9, %0\n\tv_cmp_lt_u32_sdwa vcc, %0, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cmp_eq_u32_e64 %17, %19, %18\n\tv_cmp_gt_i16_e64 %17, 0, %0\n\tv_cndmask_b32 %0, %0, %18, vcc\n\tv_and_or_b32 %16, %1, %8, %20\n\tv_and_b32 %16, %9, %1\n\tv_cmp_lt_u32_sdwa vcc, %1, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cmp_eq_u32_e64 %17, %19, %18\n\tv_cmp_gt_i16_e64 %17, 0, %1\n\tv_cndmask_b32 %1, %1, %18, vcc\n\tv_and_or_b32 %16, %2, %8, %20\n\tv_and_b32 %16, %9, %2\n\tv_cmp_lt_u32_sdwa vcc, %2, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cmp_eq_u32_e64 %17, %19, %18\n\tv_cmp_gt_i16_e64 %17, 0, %2\n\tv_cndmask_b32 %2, %2, %18, vcc\n\tv_and_or_b32 %16, %3, %8, %20\n\tv_and_b32 %16, %9, %3\n\tv_cmp_lt_u32_sdwa vcc, %3, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cmp_eq_u32_e64 %17, %19, %18\n\tv_cmp_gt_i16_e64 %17, 0, %3\n\tv_cndmask_b32 %3, %3, %18, vcc\n\tv_and_or_b32 %16, %4, %8, %20\n\tv_and_b32 %16, %9, %4\n\tv_cmp_lt_u32_sdwa vcc, %4, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cmp_eq_u32_e64 %17, %19, %18\n\tv_cmp_gt_i16_e64 %17, 0, %4\n\tv_cndmask_b32 %4, %4, %18, vcc\n\tv_and_or_b32 %16, %5, %8, %20\n\tv_and_b32 %16, %9, %5\n\tv_cmp_lt_u32_sdwa vcc, %5, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cmp_eq_u32_e64 %17, %19, %18\n\tv_cmp_gt_i16_e64 %17, 0, %5\n\tv_cndmask_b32 %5, %5, %18, vcc\n\tv_and_or_b32 %16, %6, %8, %20\n\tv_and_b32 %16, %9, %6\n\tv_cmp_lt_u32_sdwa vcc, %6, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cmp_eq_u32_e64 %17, %19, %18\n\tv_cmp_gt_i16_e64 %17, 0, %6\n\tv_cndmask_b32 %6, %6, %18, vcc\n\tv_and_or_b32 %16, %7, %8, %20\n\tv_and_b32 %16, %9, %7\n\tv_cmp_lt_u32_sdwa vcc, %7, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cmp_eq_u32_e64 %17, %19, %18\n\tv_cmp_gt_i16_e64 %17, 0, %7\n\tv_cndmask_b32 %7, %7, %18, vcc" ROUND_OPERANDS);
+      if (OP == 39) asm volatile("v_and_or_b32 %16, %0, %19, %20\n\tv_and_b32 %16, 0x7f8, %0\n\tv_cmp_lt_u32_sdwa vcc, %0, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cmp_eq_u32_e64 %17, %19, %18\n\tv_cmp_gt_i16_e64 %17, 0, %0\n\tv_cndmask_b32 %0, %0, %18, vcc\n\tv_and_or_b32 %16, %1, %19, %20\n\tv_and_b32 %16, 0x7f8, %1\n\tv_cmp_lt_u32_sdwa vcc, %1, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cmp_eq_u32_e64 %17, %19, %18\n\tv_cmp_gt_i16_e64 %17, 0, %1\n\tv_cndmask_b32 %1, %1, %18, vcc\n\tv_and_or_b32 %16, %2, %19, %20\n\tv_and_b32 %16, 0x7f8, %2\n\tv_cmp_lt_u32_sdwa vcc, %2, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cmp_eq_u32_e64 %17, %19, %18\n\tv_cmp_gt_i16_e64 %17, 0, %2\n\tv_cndmask_b32 %2, %2, %18, vcc\n\tv_and_or_b32 %16, %3, %19, %20\n\tv_and_b32 %16, 0x7f8, %3\n\tv_cmp_lt_u32_sdwa vcc, %3, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cmp_eq_u32_e64 %17, %19, %18\n\tv_cmp_gt_i16_e64 %17, 0, %3\n\tv_cndmask_b32 %3, %3, %18, vcc\n\tv_and_or_b32 %16, %4, %19, %20\n\tv_and_b32 %16, 0x7f8, %4\n\tv_cmp_lt_u32_sdwa vcc, %4, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cmp_eq_u32_e64 %17, %19, %18\n\tv_cmp_gt_i16_e64 %17, 0, %4\n\tv_cndmask_b32 %4, %4, %18, vcc\n\tv_and_or_b32 %16, %5, %19, %20\n\tv_and_b32 %16, 0x7f8, %5\n\tv_cmp_lt_u32_sdwa vcc, %5, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cmp_eq_u32_e64 %17, %19, %18\n\tv_cmp_gt_i16_e64 %17, 0, %5\n\tv_cndmask_b32 %5, %5, %18, vcc\n\tv_and_or_b32 %16, %6, %19, %20\n\tv_and_b32 %16, 0x7f8, %6\n\tv_cmp_lt_u32_sdwa vcc, %6, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cmp_eq_u32_e64 %17, %19, %18\n\tv_cmp_gt_i16_e64 %17, 0, %6\n\tv_cndmask_b32 %6, %6, %18, vcc\n\tv_and_or_b32 %16, %7, %19, %20\n\tv_and_b32 %16, 0x7f8, %7\n\tv_cmp_lt_u32_sdwa vcc, %7, %18 src0_sel:WORD_1 src1_sel:DWORD\n\tv_cmp_eq_u32_e64 %17, %19, %18\n\tv_cmp_gt_i16_e64 %17, 0, %7\n\tv_cndmask_b32 %7, %7, %18, vcc" ROUND_OPERANDS);
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -184,6 +197,14 @@ int main() {
     run<29>("level 0 vgpr children (or, cmp sgpr, cndmask)", 3, d, st, c, w);
     run<30>("level 0 arithmetic (or, sub sgpr, ashr, and sgpr, xor sgpr)", 5, d, st, c, w);
     run<31>("v_add_u32 with a uniform global_load_dwordx2 (saddr, voffset 0) every 8", 1, d, st, c, w);
+    run<32>("v_and_b32 vgpr", 1, d, st, c, w);
+    run<33>("v_and_or_b32 vgpr mask", 1, d, st, c, w);
+    run<34>("v_and_b32 vgpr + v_or_b32 vgpr", 2, d, st, c, w);
+    run<35>("step fixed vgpr masks (and_or, and, cmp_sdwa, cndmask)", 4, d, st, c, w);
+    run<36>("level 0 arithmetic + addresses (sub, ashr, and, xor sgpr; and_or sgpr mask, and literal)", 6, d, st, c, w);
+    run<37>("level 0 arithmetic + addresses, vgpr masks", 6, d, st, c, w);
+    run<38>("step NaN vgpr masks (and_or, and, cmp_sdwa, cmp_eq e64, cmp_gt_i16 e64, cndmask)", 6, d, st, c, w);
+    run<39>("step NaN (and_or sgpr mask, and literal, cmp_sdwa, cmp_eq e64, cmp_gt_i16 e64, cndmask)", 6, d, st, c, w);
   }
   return 0;
 }
