@@ -141,6 +141,25 @@
  * a tree in the accumulator type, so a stage is a snapshot of the chain the
  * whole forest runs, and the stages of one call cost one walk of the forest and
  * one replay of the chain.
+ *
+ * Prediction early stopping (ABI 15; TI_OUTPUT_EARLY_STOP: LightGBM's
+ * pred_early_stop / pred_early_stop_freq / pred_early_stop_margin, restated from
+ * gbdt_prediction.cpp, prediction_early_stop.cpp and predictor.hpp).  With the
+ * round R >= 1 (trees) and the threshold m of ti_forest_set_early_stop, a row's
+ * accumulators run TI_OUTPUT_MARGIN's chain: they start from the base under
+ * base_first and take one leaf add a tree, in tree order, in the accumulator
+ * type.  After trees R-1, 2R-1, 3R-1, ... -- not after a shorter tail -- the
+ * accumulators, widened to double, are tested:
+ *   K == 1: the row stops iff 2.0 * fabs(acc[0]) > m;
+ *   K > 1:  with a >= b the two largest of acc[0..K) by value, the row stops
+ *           iff a - b > m (a tie of the top two gives 0).
+ * Both comparisons are strict, and a row with a NaN accumulator never stops.
+ * A stopped row adds no further tree; its accumulators are then finished as any
+ * margin is: base_first = 0 adds the base, average_divisor is the forest's (the
+ * whole tree count of LightGBM's rf mode, not the trees walked), and the
+ * transform applies when asked for.  R >= T or m = +inf give TI_OUTPUT_MARGIN's
+ * bits.  The rule is the library's; which models may take it (LightGBM: the
+ * binary, multiclass and ranking objectives) is the host's to decide.
  */
 #ifndef TREEINFER_H_
 #define TREEINFER_H_
@@ -151,7 +170,7 @@
 extern "C" {
 #endif
 
-#define TI_ABI_VERSION 14
+#define TI_ABI_VERSION 15
 
 /* return codes */
 #define TI_OK               0
@@ -294,6 +313,22 @@ extern "C" {
                               /* then counts.  The host pipeline sizes its row    */
                               /* chunks by the widest of the input row, the 4 * T */
                               /* bytes of leaf ids and the S * W outputs.         */
+#define TI_OUTPUT_EARLY_STOP 9
+                              /* ABI 15: the rule above with the state of         */
+                              /* ti_forest_set_early_stop, [rows, W] in the       */
+                              /* accumulator type: W as TI_OUTPUT_MARGIN's, or as */
+                              /* TI_OUTPUT_PREDICT's when transformed.  Two calls */
+                              /* give the same bits.  TI_ERR_UNSUPPORTED, the     */
+                              /* handle serving on, for linear leaves, pre-steps, */
+                              /* more than 16 output groups and from              */
+                              /* ti_predict_csr.  TI_OPT_SMALL_BATCH_ROWS does    */
+                              /* not route it.  The first call uploads the        */
+                              /* layout-1 node set of a forest on another layout  */
+                              /* (shared with ti_predict_csr and the small-batch  */
+                              /* walk), which ti_forest_info.device_bytes then    */
+                              /* counts.  The host pipeline sizes its row chunks  */
+                              /* by the wider of the input row and the 4 + K      */
+                              /* accumulators a row keeps between two launches.   */
 
 /*
  * Canonical forest: host structure-of-arrays over the nodes of all trees,
@@ -417,6 +452,11 @@ typedef struct ti_forest_info {
                                  tree-parallel walk has served a call, -1 the forest
                                  keeps its own path at every size (linear leaves,
                                  pre-steps, more than 16 output groups)               */
+  int32_t early_stop_walk;    /* ABI 15, TI_OUTPUT_EARLY_STOP: 0 no call of the kind yet,
+                                 1 the layout-1 node set is resident and the
+                                 round-checked walk has served a call, -1 the forest
+                                 refuses the kind (linear leaves, pre-steps, more than
+                                 16 output groups)                                     */
 } ti_forest_info;
 
 /* ti_forest_set_option options (ABI 4) */
@@ -509,6 +549,21 @@ int ti_forest_set_quantiles(ti_forest* forest, const double* q, int32_t n_q);
 int ti_forest_set_stages(ti_forest* forest, int32_t begin, const int32_t* ends,
                          int32_t n_stages, int32_t transformed);
 
+/* ABI 15: the state of TI_OUTPUT_EARLY_STOP.  round_trees >= 1 is the round R
+ * in trees (LightGBM's pred_early_stop_freq counts iterations: R = freq x trees
+ * per iteration); margin_threshold is m, any value but NaN (a negative m stops
+ * every row at the first test, +inf none); transformed is 0 (the answer as
+ * TI_OUTPUT_MARGIN) or 1 (as TI_OUTPUT_PREDICT).  Anything else is
+ * TI_ERR_INVALID and the forest keeps its state.  The default is round_trees =
+ * T, margin_threshold = +inf, transformed = 0: the whole forest's margin.
+ * Handle state, as ti_forest_set_stages is: call it with no
+ * TI_OUTPUT_EARLY_STOP call (and no ti_output_shape for that kind) in flight on
+ * the forest; no other kind reads it.  A call of the kind is a fixed sequence of
+ * launches with no host readback, so ti_predict_device stays asynchronous.
+ * Replaces pred_early_stop* of LGBM_BoosterPredictForMat's parameter string. */
+int ti_forest_set_early_stop(ti_forest* forest, int32_t round_trees, double margin_threshold,
+                             int32_t transformed);
+
 /* Per-forest tuning that changes speed, never results (both TreeSHAP kernels
  * produce the same contributions).  0 or TI_ERR_INVALID for an unknown option
  * or a negative value.  Replaces nothing in the libraries: xgboost and
@@ -549,7 +604,7 @@ int ti_predict(ti_forest* forest, const void* X, int32_t x_dtype, int64_t n_rows
  * and TI_OUTPUT_LEAF of any forest the float explicit kernel can walk
  * (numerical splits, both categorical rules, vector leaves, multiclass groups,
  * either accumulator, lgb_zero_map).  TI_ERR_UNSUPPORTED, the handle serving
- * on, for every other output kind (TI_OUTPUT_STAGED too) and for forests with linear leaves, pre-steps,
+ * on, for every other output kind (TI_OUTPUT_STAGED and TI_OUTPUT_EARLY_STOP too) and for forests with linear leaves, pre-steps,
  * tree weights or more than 16 output groups (group parts).  The first call
  * builds the forest's sparse image on every device, which
  * ti_forest_info.device_bytes then counts.  Thread-safe per handle.

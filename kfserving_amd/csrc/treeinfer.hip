@@ -27,6 +27,7 @@
 #include "treeinfer_pre.h"
 #include "treeinfer_sparse.h"
 #include "treeinfer_small.h"
+#include "treeinfer_estop.h"
 
 namespace {
 
@@ -229,6 +230,7 @@ int64_t output_width(const ti_forest* f, int kind) {
   if (kind == TI_OUTPUT_TREE_QUANTILE) return static_cast<int64_t>(f->quant_q.size());
   if (kind == TI_OUTPUT_STAGED)
     return static_cast<int64_t>(f->stage_ends.size()) * stage_width(f);
+  if (kind == TI_OUTPUT_EARLY_STOP && f->es_transformed && f->transform == TI_TRANSFORM_ARGMAX) return 1;
   if (kind == TI_OUTPUT_PREDICT && f->transform == TI_TRANSFORM_ARGMAX) return 1;
   return f->K;
 }
@@ -601,15 +603,17 @@ int64_t chunk_rows(size_t row_bytes) {
 // Quantiles across trees write a few elements a row, but a row holds 4 * T
 // bytes of leaf ids between the two passes: that scratch row takes the output
 // row's place.  Staged predictions hold the same scratch row and write S * W
-// elements a row: the wider of the two counts.
+// elements a row: the wider of the two counts.  Early stopping keeps a row id
+// and the K accumulators a row in its survivor lists: that entry counts.
 int64_t chunk_rows_for(const ti_forest* f, int xdt, int64_t stride, int kind) {
   const size_t x_row = static_cast<size_t>(stride) * dtype_size(xdt);
   if (kind != TI_OUTPUT_INTERACT && kind != TI_OUTPUT_CONTRIB_APPROX && kind != TI_OUTPUT_TREE_QUANTILE &&
-      kind != TI_OUTPUT_STAGED)
+      kind != TI_OUTPUT_STAGED && kind != TI_OUTPUT_EARLY_STOP)
     return chunk_rows(x_row);
   size_t o_row = dtype_size(output_dtype(f, kind)) * static_cast<size_t>(output_width(f, kind));
   if (kind == TI_OUTPUT_TREE_QUANTILE) o_row = static_cast<size_t>(4) * f->T;
   if (kind == TI_OUTPUT_STAGED) o_row = std::max(o_row, static_cast<size_t>(4) * f->T);
+  if (kind == TI_OUTPUT_EARLY_STOP) o_row = 4 + static_cast<size_t>(f->K) * dtype_size(f->accum);
   const int mb = env_int("TI_CHUNK_MB", 64);
   const int64_t r = static_cast<int64_t>((static_cast<size_t>(std::max(mb, 1)) << 20) /
                                          std::max<size_t>(std::max(x_row, o_row), 1));
@@ -1110,6 +1114,102 @@ int launch_small(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t 
   hipLaunchKernelGGL(fn, dim3(static_cast<unsigned>(rows)), dim3(p.block), p.lds, stream, p.a);
   TI_HIP(hipGetLastError());
   f->small_served.store(true, std::memory_order_relaxed);
+  return TI_OK;
+}
+
+// ------------------------------------------------------------ early stopping
+// TI_OUTPUT_EARLY_STOP (treeinfer_estop.h).  The plan: 256-row
+// tiles; the feature image in LDS while it takes at most half of a workgroup's
+// share (two workgroups a CU, the share of the staged layouts); the rest of the
+// share is the two node buffers, within the lanes' prefetch registers.
+void plan_estop(const ti_forest* f, const DeviceForest& d, int xdt, LaunchPlan* p) {
+  plan_model(f, d, xdt, f->es_transformed ? TI_OUTPUT_PREDICT : TI_OUTPUT_MARGIN, p);
+  const size_t xs = dtype_size(xdt);
+  const size_t share = kLdsPerCu / 2 - 16;
+  const size_t fb = ti::estop_feat_bytes(f->F, xs);
+  p->R = ti::kEsRows;
+  p->block = ti::kEsRows;
+  p->key.walk = ti::Walk::EarlyStop;
+  p->key.feat_lds = fb <= share / 2;
+  const size_t room = share - (p->key.feat_lds ? fb : 0);
+  const size_t cap = std::min<size_t>(ti::kEsMaxCap, room / (2 * ti::estop_node_bytes(xs))) & ~size_t(15);
+  p->lds = ti::estop_lds_bytes(p->key.feat_lds ? fb : 0, cap, xs);
+  KArgs& a = p->a;
+  a.nodes = d.sp_ex.nodes;
+  a.thr64 = d.sp_ex.thr64;
+  a.node_base = d.sp_ex.node_base;
+  a.root = d.sp_ex.root;
+  a.leaf_base = d.sp_ex.leaf_base;
+  a.leaves = d.sp_ex.leaves;
+  a.cat_words = d.sp_ex.cat_words;
+  a.sp_node_last = f->sparse_node_last;
+  a.es_round = f->es_round;
+  a.es_margin = f->es_margin;
+  a.es_cap = static_cast<int32_t>(cap);
+}
+
+// A block of rows is walked segment after segment of kEsSegRounds rounds, each
+// a launch over the survivors of the one before: two lists that alternate and a
+// count a segment, in one scratch buffer of the replica's pool, at most 1 GiB.
+// Every launch has the grid of the whole block; nothing is read back.
+int launch_estop(ti_forest* f, DeviceForest& d, const void* X, int xdt, int64_t rows, int32_t cols,
+                 int64_t stride, void* out, hipStream_t stream) {
+  if (f->small_routed)
+    return fail(TI_ERR_UNSUPPORTED,
+                "TI_OUTPUT_EARLY_STOP of a forest with linear leaves, pre-steps or more than " +
+                    std::to_string(ti::kMaxGroups) + " output groups");
+  if (rows <= 0) return TI_OK;
+  int rc = ensure_small(f);
+  if (rc) return rc;
+  LaunchPlan p;
+  plan_estop(f, d, xdt, &p);
+  KernelFn fn = ti::select(p.key);
+  if ((rc = ensure_lds_attr(d.device, fn))) return rc;
+  occ_note(fn, p.block, p.lds);
+  const size_t xs = dtype_size(xdt), as = dtype_size(f->accum);
+  const int64_t n_rounds = (static_cast<int64_t>(f->T) + f->es_round - 1) / f->es_round;
+  const int n_seg = static_cast<int>((n_rounds + ti::kEsSegRounds - 1) / ti::kEsSegRounds);
+  const size_t entry = 4 + static_cast<size_t>(f->K) * as;
+  int64_t rows_block = static_cast<int64_t>((size_t(1) << 29) / entry);
+  rows_block = std::max<int64_t>(p.R, rows_block / p.R * p.R);
+  const int64_t cap = (std::min(rows, rows_block) + p.R - 1) / p.R * p.R;
+  const size_t list_bytes = ti::estop_list_bytes(static_cast<size_t>(cap), f->K, as);
+  ScratchHold buf(d, stream);   // given back behind the last segment
+  unsigned char* lists = nullptr;
+  uint32_t* counts = nullptr;
+  if (n_seg > 1) {
+    if (!buf.take(2 * list_bytes + static_cast<size_t>(n_seg) * 4))
+      return fail(TI_ERR_NOMEM, "survivor-list scratch allocation failed");
+    lists = static_cast<unsigned char*>(buf.p);
+    counts = reinterpret_cast<uint32_t*>(lists + 2 * list_bytes);
+  }
+  const size_t out_row = static_cast<size_t>(output_width(f, TI_OUTPUT_EARLY_STOP)) * as;
+  p.a.row_stride = stride;
+  p.a.n_cols = cols;
+  p.a.es_list_cap = cap;
+  for (int64_t b0 = 0; b0 < rows; b0 += rows_block) {
+    const int64_t nb = std::min(rows_block, rows - b0);
+    p.a.X = static_cast<const unsigned char*>(X) + static_cast<size_t>(b0 * stride) * xs;
+    p.a.out = static_cast<unsigned char*>(out) + static_cast<size_t>(b0) * out_row;
+    p.a.n_rows = nb;
+    const unsigned grid = static_cast<unsigned>((nb + p.R - 1) / p.R);
+    if (n_seg > 1) {
+      hipLaunchKernelGGL(ti::estop_clear_kernel, dim3((n_seg + 255) / 256), dim3(256), 0, stream, counts, n_seg);
+      TI_HIP(hipGetLastError());
+    }
+    for (int s = 0; s < n_seg; ++s) {   // segment s reads list s & 1 and count s, writes the others
+      p.a.es_r0 = s * ti::kEsSegRounds;
+      p.a.es_r1 = static_cast<int32_t>(std::min<int64_t>(n_rounds, p.a.es_r0 + ti::kEsSegRounds));
+      p.a.es_last = s == n_seg - 1;
+      p.a.es_in = s == 0 ? nullptr : lists + static_cast<size_t>(s & 1) * list_bytes;
+      p.a.es_in_n = s == 0 ? nullptr : counts + s;
+      p.a.es_out = p.a.es_last ? nullptr : lists + static_cast<size_t>((s + 1) & 1) * list_bytes;
+      p.a.es_out_n = p.a.es_last ? nullptr : counts + s + 1;
+      hipLaunchKernelGGL(fn, dim3(grid), dim3(p.block), p.lds, stream, p.a);
+      TI_HIP(hipGetLastError());
+    }
+  }
+  f->estop_served.store(true, std::memory_order_relaxed);
   return TI_OK;
 }
 
@@ -1778,6 +1878,8 @@ int launch_walk(ti_forest* f, int slot, const void* X, int xdt, int64_t rows, in
     if (!f->parts.empty()) return fail(TI_ERR_UNSUPPORTED, f->staged_refused);
     return launch_staged(f, *f->devs[slot], X, xdt, rows, cols, stride, out, stream);
   }
+  if (kind == TI_OUTPUT_EARLY_STOP)   // a forest in group parts is refused there: small_routed
+    return launch_estop(f, *f->devs[slot], X, xdt, rows, cols, stride, out, stream);
   if (kind == TI_OUTPUT_CONTRIB && f->linear)
     return fail(TI_ERR_UNSUPPORTED,
                 "TI_OUTPUT_CONTRIB of a forest with linear leaves (LightGBM itself refuses "
@@ -2102,6 +2204,20 @@ int ti_forest_set_stages(ti_forest* f, int32_t begin, const int32_t* ends, int32
   return TI_OK;
 }
 
+int ti_forest_set_early_stop(ti_forest* f, int32_t round_trees, double margin_threshold,
+                             int32_t transformed) {
+  if (!f) return fail(TI_ERR_INVALID, "null forest");
+  if (round_trees < 1) return fail(TI_ERR_INVALID, "early stop: round_trees must be >= 1");
+  if (margin_threshold != margin_threshold)
+    return fail(TI_ERR_INVALID, "early stop: margin_threshold must not be NaN");
+  if (transformed != 0 && transformed != 1)
+    return fail(TI_ERR_INVALID, "early stop: transformed must be 0 or 1");
+  f->es_round = round_trees;
+  f->es_margin = margin_threshold;
+  f->es_transformed = transformed;
+  return TI_OK;
+}
+
 int ti_forest_get_info(const ti_forest* f, ti_forest_info* info) {
   if (!f || !info) return fail(TI_ERR_INVALID, "null argument");
   info->layout = f->layout;
@@ -2149,6 +2265,8 @@ int ti_forest_get_info(const ti_forest* f, ti_forest_info* info) {
     info->sparse_walk[i] = !sp ? 0 : t.search ? 2 : 1;
     info->sparse_rows[i] = sp ? t.R : 0;
   }
+  info->early_stop_walk = f->small_routed ? -1
+                          : f->ex_ready.load(std::memory_order_acquire) && f->estop_served.load() ? 1 : 0;
   info->small_walk = f->small_routed ? -1
                      : f->ex_ready.load(std::memory_order_acquire) && f->small_served.load() ? 1 : 0;
   return TI_OK;
@@ -2190,7 +2308,7 @@ int ti_forest_set_option(ti_forest* f, int32_t option, int64_t value) {
 int ti_output_shape(const ti_forest* f, int32_t kind, int64_t n_rows, int64_t* out_len,
                     int32_t* out_dtype) {
   if (!f || !out_len || !out_dtype) return fail(TI_ERR_INVALID, "null argument");
-  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_STAGED) return fail(TI_ERR_INVALID, "bad output kind");
+  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_EARLY_STOP) return fail(TI_ERR_INVALID, "bad output kind");
   if (n_rows < 0) return fail(TI_ERR_INVALID, "negative n_rows");
   *out_len = n_rows * output_width(f, kind);
   *out_dtype = output_dtype(f, kind);
@@ -2201,7 +2319,7 @@ static int check_call(const ti_forest* f, const void* X, int32_t xdt, int64_t ro
                       int64_t stride, int32_t kind, const void* out, int64_t out_len) {
   if (!f) return fail(TI_ERR_INVALID, "null forest");
   if (xdt != TI_F32 && xdt != TI_F64) return fail(TI_ERR_INVALID, "x_dtype must be TI_F32 or TI_F64");
-  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_STAGED) return fail(TI_ERR_INVALID, "bad output kind");
+  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_EARLY_STOP) return fail(TI_ERR_INVALID, "bad output kind");
   if (rows < 0) return fail(TI_ERR_INVALID, "negative n_rows");
   if (rows == 0) return TI_OK;
   if (!X || !out) return fail(TI_ERR_INVALID, "null data pointer");
@@ -2269,7 +2387,7 @@ int ti_predict_csr(ti_forest* f, const int64_t* indptr, const int32_t* indices, 
   if (xdt != TI_F32 && xdt != TI_F64) return fail(TI_ERR_INVALID, "x_dtype must be TI_F32 or TI_F64");
   if (absent != TI_CSR_ABSENT_ZERO && absent != TI_CSR_ABSENT_NAN)
     return fail(TI_ERR_INVALID, "absent must be TI_CSR_ABSENT_ZERO or TI_CSR_ABSENT_NAN");
-  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_STAGED) return fail(TI_ERR_INVALID, "bad output kind");
+  if (kind < TI_OUTPUT_MARGIN || kind > TI_OUTPUT_EARLY_STOP) return fail(TI_ERR_INVALID, "bad output kind");
   if (kind != TI_OUTPUT_MARGIN && kind != TI_OUTPUT_PREDICT && kind != TI_OUTPUT_LEAF)
     return fail(TI_ERR_UNSUPPORTED, "CSR rows serve TI_OUTPUT_MARGIN, TI_OUTPUT_PREDICT and "
                                     "TI_OUTPUT_LEAF; output kind " + std::to_string(kind) +

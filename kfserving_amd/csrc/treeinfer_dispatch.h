@@ -3,8 +3,9 @@
 // accumulator type) pair, treeinfer_k_cat.hip the categorical heap's,
 // treeinfer_k_crec.hip the categorical records', treeinfer_k_obliv.hip the
 // oblivious trees', treeinfer_k_sparse.hip the CSR walk's and
-// treeinfer_k_small.hip the small-batch walk's for all four pairs, so the nine
-// compile in parallel.
+// treeinfer_k_small.hip the small-batch walk's for all four pairs (and
+// treeinfer_k_staged.hip / treeinfer_k_estop.hip the staged pass's and the
+// early-stopping walk's), so they all compile in parallel.
 //
 // The host names what it launches with a KernelKey; ti::select(key) is the one
 // way from a key to a kernel.  Each rule that turns a runtime value into a
@@ -44,13 +45,14 @@ enum class Walk {
   SparseSearch,     // CSR rows, each column searched in its row   (treeinfer_sparse.h)
   TreeLanes,        // small batches: a lane a tree, a workgroup a row  tree_lanes_predict_kernel
   StagedAccum,      // TI_OUTPUT_STAGED's pass 2 over leaf ids   staged_accum_kernel
+  EarlyStop,        // TI_OUTPUT_EARLY_STOP: rounds of trees, a test a round  estop_walk_kernel
 };
 
 struct KernelKey {
   Walk walk;
   bool x64, acc64;   // float64 input / sums (else float32)
   int K;             // output groups
-  bool feat_lds;     // Heap, Explicit: feature image in LDS; TreeLanes: the row in LDS
+  bool feat_lds;     // Heap, Explicit, EarlyStop: feature image in LDS; TreeLanes: the row in LDS
   bool zero_rule;    // LightGBM zero rule (no binned heap walk has one)
   bool bins16;       // BinHeap, BinHeapFixed, HeapTopStaged: u16 bins (else u8)
   int ilp;           // record walks and bottoms: trees a lane walks at once
@@ -157,6 +159,8 @@ KernelFn select_walk(const KernelKey& k) {
       break;   // kernels_small
     case Walk::StagedAccum:
       break;   // kernels_staged
+    case Walk::EarlyStop:
+      break;   // kernels_estop
   }
   return nullptr;
 }
@@ -178,6 +182,7 @@ KernelFn kernels_obliv(const KernelKey& k); // the oblivious trees, every pair
 KernelFn kernels_sparse(const KernelKey& k);// the CSR walk, every pair
 KernelFn kernels_small(const KernelKey& k); // the small-batch walk, every pair
 KernelFn kernels_staged(const KernelKey& k);// the staged pass, both accumulators
+KernelFn kernels_estop(const KernelKey& k); // the round-checked walk, every pair
 
 inline KernelFn select(const KernelKey& k) {
   if (k.walk == Walk::CatHeapXgb || k.walk == Walk::CatHeapLgb) return kernels_cat(k);
@@ -186,6 +191,7 @@ inline KernelFn select(const KernelKey& k) {
   if (k.walk == Walk::SparseImage || k.walk == Walk::SparseSearch) return kernels_sparse(k);
   if (k.walk == Walk::TreeLanes) return kernels_small(k);
   if (k.walk == Walk::StagedAccum) return kernels_staged(k);
+  if (k.walk == Walk::EarlyStop) return kernels_estop(k);
   if (!k.x64) return k.acc64 ? kernels_fd(k) : kernels_ff(k);
   return k.acc64 ? kernels_dd(k) : kernels_df(k);
 }

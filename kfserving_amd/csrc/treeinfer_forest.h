@@ -744,6 +744,15 @@ struct ti_forest {
   std::atomic<int64_t> small_rows{std::max(env_int("TI_SMALL_BATCH_ROWS", 0), 0)};
   bool small_routed = false;
   std::atomic<bool> small_served{false};
+  // Prediction early stopping (TI_OUTPUT_EARLY_STOP, treeinfer_estop.h): the
+  // round, the threshold and whether the answer is transformed, written by
+  // ti_forest_set_early_stop with no call of the kind in flight (fill_model sets
+  // the default: T, +inf, 0).  The walk reads the layout-1 set above and is
+  // refused where the small-batch walk is routed away (small_routed);
+  // estop_served: it has answered a call.
+  int32_t es_round = 1, es_transformed = 0;
+  double es_margin = 0.0;
+  std::atomic<bool> estop_served{false};
   struct SparseSource {
     ti_forest_desc desc;
     std::vector<int64_t> tree_offset, cat_offset;

@@ -155,6 +155,18 @@ struct KArgs {
   int32_t st_n;                   // stages S
   int32_t st_width;               // outputs a stage W
   int32_t st_tile;                // elements a row of the LDS output tile holds
+  // the round-checked walk (TI_OUTPUT_EARLY_STOP, treeinfer_estop.h), after them
+  // for the same reason.  `nodes` ... `cat_words` are the layout-1 set.
+  int32_t es_round;               // trees a round R
+  int32_t es_r0, es_r1;           // the rounds [es_r0, es_r1) of this launch
+  int32_t es_cap;                 // nodes one of the two LDS buffers holds
+  int32_t es_last;                // the forest ends with this launch: survivors are finished
+  double es_margin;               // the test's threshold m
+  int64_t es_list_cap;            // entries a survivor list holds (its column pitch)
+  const void* es_in;              // the list this launch walks; null: rows of X directly
+  const uint32_t* es_in_n;        // its count
+  void* es_out;                   // the list of the survivors of this launch
+  uint32_t* es_out_n;             // its count
 };
 
 __device__ __forceinline__ size_t align16(size_t x) { return (x + 15) & ~size_t(15); }

@@ -139,6 +139,9 @@ void fill_model(const ti_forest_desc* desc, const std::vector<int>& depth, ti_fo
   f->stage_begin = 0;   // TI_OUTPUT_STAGED's default: the whole forest's margin
   f->stage_transformed = 0;
   f->stage_ends.assign(1, desc->n_trees);
+  f->es_round = std::max(desc->n_trees, 1);   // TI_OUTPUT_EARLY_STOP's default: one round, no test that matters
+  f->es_margin = std::numeric_limits<double>::infinity();
+  f->es_transformed = 0;
   if (f->K <= ti::kMaxGroups)
     for (int k = 0; k < f->K; ++k) f->base[k] = desc->base_margin[k];
   for (int64_t i = 0; i < desc->n_nodes; ++i)

@@ -18,11 +18,11 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .forest import (Forest, OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_CONTRIB_INTERV, OUT_INTERACT,
+from .forest import (Forest, OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_CONTRIB_INTERV, OUT_EARLY_STOP, OUT_INTERACT,
                      OUT_LEAF, OUT_MARGIN, OUT_PREDICT, OUT_STAGED, OUT_TREE_QUANTILE,
                      TI_F32, TI_F64, TI_I32)
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 _LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
 LIB_PATH = os.environ.get("TREEINFER_LIB", os.path.join(_LIB_DIR, "libtreeinfer.so"))
 
@@ -31,7 +31,7 @@ EXPORTED_SYMBOLS = (
     "ti_predict", "ti_predict_device", "ti_transform_device", "ti_last_error", "ti_device_count",
     "ti_abi_version", "ti_forest_set_option", "ti_pretransform_device",
     "ti_forest_set_background", "ti_forest_set_quantiles", "ti_predict_csr",
-    "ti_forest_set_stages",
+    "ti_forest_set_stages", "ti_forest_set_early_stop",
 )
 
 # ti_predict_csr: what an entry the matrix does not store reads as
@@ -121,6 +121,7 @@ class _ForestInfo(ctypes.Structure):
         ("sparse_walk", ctypes.c_int32 * 2),
         ("sparse_rows", ctypes.c_int32 * 2),
         ("small_walk", ctypes.c_int32),
+        ("early_stop_walk", ctypes.c_int32),
     ]
 
 
@@ -173,6 +174,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.ti_forest_set_quantiles.argtypes = [vp, vp, i32]
         lib.ti_forest_set_stages.restype = ctypes.c_int
         lib.ti_forest_set_stages.argtypes = [vp, i32, vp, i32, i32]
+        lib.ti_forest_set_early_stop.restype = ctypes.c_int
+        lib.ti_forest_set_early_stop.argtypes = [vp, i32, ctypes.c_double, i32]
         if lib.ti_abi_version() != ABI_VERSION:
             raise TreeInferError(-1, f"ABI mismatch: library {lib.ti_abi_version()}, "
                                      f"binding {ABI_VERSION}")
@@ -286,6 +289,8 @@ class DeviceForest:
         self.quantiles = (0.5,)     # this handle's OUT_TREE_QUANTILE levels (set_quantiles)
         # this handle's OUT_STAGED stages (set_stages): begin, ends, transformed
         self.stages = (0, (f.n_trees,), False)
+        # this handle's OUT_EARLY_STOP state (set_early_stop): round_trees, margin, transformed
+        self.early_stop = (max(f.n_trees, 1), float("inf"), False)
 
     # ------------------------------------------------------------------ info
     def info(self) -> dict:
@@ -345,6 +350,25 @@ class DeviceForest:
         the stages are transformed."""
         return self.forest.output_width(OUT_PREDICT if self.stages[2] else OUT_MARGIN)
 
+    def set_early_stop(self, round_trees: int, margin: float, transformed: bool = False) -> None:
+        """ti_forest_set_early_stop: OUT_EARLY_STOP then tests a row after every
+        ``round_trees`` trees and stops adding trees to it once
+        ``2 * |margin sum|`` (one group) or the gap of its two largest sums
+        exceeds ``margin`` -- LightGBM's pred_early_stop, whose
+        pred_early_stop_freq counts iterations, not trees.  The answer is the
+        stopped row's OUT_MARGIN, or its OUT_PREDICT when ``transformed``.
+        Call it with no predict in flight on this forest."""
+        _check(self._lib, self._lib.ti_forest_set_early_stop(self._handle, int(round_trees),
+                                                             float(margin), 1 if transformed else 0))
+        self.early_stop = (int(round_trees), float(margin), bool(transformed))
+
+    def _width(self, kind: int) -> int:
+        if kind == OUT_STAGED:
+            return len(self.stages[1]) * self.stage_width()
+        if kind == OUT_EARLY_STOP:
+            return self.forest.output_width(OUT_PREDICT if self.early_stop[2] else OUT_MARGIN)
+        return len(self.quantiles) if kind == OUT_TREE_QUANTILE else self.forest.output_width(kind)
+
     def linear_tile_rows(self, x_dtype) -> int:
         """Rows per tile of the linear-leaf pass (launch_linear in
         treeinfer.hip) for input of ``x_dtype``: the largest of 256 / 128 / 64
@@ -379,10 +403,7 @@ class DeviceForest:
             return self._predict_csr(X, kind, CSR_ABSENT[absent])
         X = self.prepare_input(X)
         rows, cols = X.shape
-        if kind == OUT_STAGED:
-            width = len(self.stages[1]) * self.stage_width()
-        else:
-            width = len(self.quantiles) if kind == OUT_TREE_QUANTILE else self.forest.output_width(kind)
+        width = self._width(kind)
         out = np.empty(rows * width, dtype=self.forest.output_dtype(kind))
         xdt = TI_F32 if X.dtype == np.float32 else TI_F64
         if rows:
@@ -408,9 +429,9 @@ class DeviceForest:
         indices = np.ascontiguousarray(csr.indices, dtype=np.int32)
         data = np.ascontiguousarray(csr.data, dtype=np.float32 if csr.data.dtype == np.float32
                                     else np.float64)
-        # the library refuses OUT_STAGED of CSR rows; it still gets a buffer of the kind's size
-        width = (len(self.stages[1]) * self.stage_width() if kind == OUT_STAGED
-                 else self.forest.output_width(kind))
+        # the library refuses OUT_STAGED and OUT_EARLY_STOP of CSR rows; it still gets a
+        # buffer of the kind's size
+        width = self._width(kind)
         out = np.empty(rows * width, dtype=self.forest.output_dtype(kind))
         if rows:
             _check(self._lib, self._lib.ti_predict_csr(
@@ -479,5 +500,5 @@ __all__ = ["DeviceForest", "TreeInferError", "prepare_input", "load_library", "d
            "OPT_SHAP_TABLE_ROWS", "OPT_SHAP_TABLE_MB", "OPT_HOST_REGISTER", "OPT_LINEAR_SCRATCH_MB",
            "OPT_SMALL_BATCH_ROWS",
            "EXPORTED_SYMBOLS", "OUT_MARGIN", "OUT_PREDICT", "OUT_LEAF", "OUT_CONTRIB", "OUT_INTERACT",
-           "OUT_CONTRIB_APPROX", "OUT_CONTRIB_INTERV", "OUT_TREE_QUANTILE", "OUT_STAGED",
+           "OUT_CONTRIB_APPROX", "OUT_CONTRIB_INTERV", "OUT_TREE_QUANTILE", "OUT_STAGED", "OUT_EARLY_STOP",
            "TI_F32", "TI_F64", "TI_I32"]

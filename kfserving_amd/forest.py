@@ -50,6 +50,7 @@ OUT_CONTRIB_APPROX = 5   # approximate (Saabas) contributions, laid out as OUT_C
 OUT_CONTRIB_INTERV = 6   # interventional TreeSHAP against a background set, laid out as OUT_CONTRIB
 OUT_TREE_QUANTILE = 7    # weighted quantiles of a row's per-tree predictions [rows, n_q]
 OUT_STAGED = 8           # the margins or predictions after chosen numbers of trees [rows, S, W]
+OUT_EARLY_STOP = 9       # LightGBM's prediction early stopping (DeviceForest.set_early_stop) [rows, W]
 TREE_QUANTILE_MAX_TREES = 4096     # the kernel's cap (treeinfer_quantile.h)
 TREE_QUANTILE_MAX_LEVELS = 8
 
@@ -339,6 +340,8 @@ class Forest:
             raise ValueError("OUT_TREE_QUANTILE's width is DeviceForest.quantiles', not the forest's")
         if kind == OUT_STAGED:          # as many as the device handle has stages
             raise ValueError("OUT_STAGED's width is DeviceForest.stages', not the forest's")
+        if kind == OUT_EARLY_STOP:      # the margin's or the prediction's: the device handle says
+            raise ValueError("OUT_EARLY_STOP's width is DeviceForest.early_stop's, not the forest's")
         if kind == OUT_PREDICT and self.transform == T_ARGMAX:
             return 1
         return self.n_groups

@@ -22,7 +22,11 @@ BOOSTER_FILE = "model.bst"
 class LightGBMModel(GPUForestMixin, KFModel):
     # request keys beside "inputs" that change the answer: KFServer sends such
     # a request to predict() alone, never through a batcher
-    unbatched_request_keys = ("start_iteration", "num_iteration")
+    unbatched_request_keys = ("start_iteration", "num_iteration", "pred_early_stop",
+                              "pred_early_stop_freq", "pred_early_stop_margin")
+    # the objectives LightGBM early-stops (NeedAccuratePrediction() is false): every
+    # other one ignores the option
+    early_stop_objectives = ("binary", "multiclass", "multiclassova", "lambdarank", "rank_xendcg")
 
     def __init__(self, name: str, model_dir: str, nthread: int, booster: Forest = None,
                  background=None):
@@ -65,7 +69,7 @@ class LightGBMModel(GPUForestMixin, KFModel):
         keys (LightGBM's own: num_iteration <= 0 or absent means every iteration
         from the start on) as a tree range; None when both are absent.  An
         iteration is num_tree_per_iteration trees."""
-        if not isinstance(request, dict) or not any(k in request for k in self.unbatched_request_keys):
+        if not isinstance(request, dict) or not any(k in request for k in ("start_iteration", "num_iteration")):
             return None
         f = self._forest
         per = int(f.meta.get("trees_per_iteration", f.n_groups))
@@ -80,10 +84,39 @@ class LightGBMModel(GPUForestMixin, KFModel):
             raise ValueError('"start_iteration" %d is beyond the model\'s %d iterations' % (b, n_iter))
         return b * per, e * per
 
+    def early_stop(self, request: Dict):
+        """The request's optional ``"pred_early_stop"`` (bool),
+        ``"pred_early_stop_freq"`` (iterations between two tests, default 10)
+        and ``"pred_early_stop_margin"`` (default 10.0), LightGBM's own, as
+        (trees a round, margin); None when the option is absent, false, or --
+        as in LightGBM -- the objective needs an accurate prediction."""
+        keys = ("pred_early_stop", "pred_early_stop_freq", "pred_early_stop_margin")
+        if not isinstance(request, dict) or not any(k in request for k in keys):
+            return None
+        on = request.get("pred_early_stop", False)
+        freq = request.get("pred_early_stop_freq", 10)
+        margin = request.get("pred_early_stop_margin", 10.0)
+        if not isinstance(on, bool):
+            raise ValueError('"pred_early_stop" must be true or false')
+        if not isinstance(freq, int) or isinstance(freq, bool) or freq < 1:
+            raise ValueError('"pred_early_stop_freq" must be an integer >= 1')
+        if isinstance(margin, bool) or not isinstance(margin, (int, float)) or margin != margin:
+            raise ValueError('"pred_early_stop_margin" must be a number')
+        if on and any(k in request for k in ("start_iteration", "num_iteration")):
+            raise ValueError('"pred_early_stop" with "start_iteration" / "num_iteration" is not served')
+        f = self._forest
+        objective = (f.objective or "").split()
+        if not on or not objective or objective[0] not in self.early_stop_objectives:
+            return None
+        return freq * int(f.meta.get("trees_per_iteration", f.n_groups)), float(margin)
+
     def predict(self, request: Dict) -> Dict:
         try:
+            stop = self.early_stop(request)
             trees = self.iteration_trees(request)
             X = self.request_matrix(request)
+            if stop is not None:
+                return {"predictions": self.predict_early_stop(X, *stop).tolist()}
             if trees is not None:
                 return {"predictions": self.predict_tree_range(X, *trees).tolist()}
             result = self.predict_matrix(X)

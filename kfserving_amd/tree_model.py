@@ -16,7 +16,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from .engine import DeviceForest, prepare_input
-from .forest import (OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_CONTRIB_INTERV, OUT_INTERACT, OUT_PREDICT,
+from .forest import (OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_CONTRIB_INTERV, OUT_EARLY_STOP, OUT_INTERACT, OUT_PREDICT,
                      OUT_STAGED, OUT_TREE_QUANTILE, Forest)
 
 BACKGROUND_FILE = "background.npy"
@@ -105,6 +105,18 @@ class GPUForestMixin:
             if dev.stages != want:
                 dev.set_stages(want[1], begin=want[0], transformed=want[2])
             return dev.predict(X, OUT_STAGED)
+
+    def predict_early_stop(self, X: np.ndarray, round_trees: int, margin: float) -> np.ndarray:
+        """OUT_EARLY_STOP, transformed: the model's prediction with rows that
+        stop walking trees once a test after every ``round_trees`` trees finds
+        them ``margin`` away from the decision boundary.  Handle state, so one
+        lock around setting it and predicting, as the staged calls take."""
+        dev = self.device_forest()
+        want = (int(round_trees), float(margin), True)
+        with self._dev_lock:
+            if dev.early_stop != want:
+                dev.set_early_stop(*want)
+            return dev.predict(X, OUT_EARLY_STOP)
 
     def predict_tree_range(self, X: np.ndarray, begin: int, end: int) -> np.ndarray:
         """The model's prediction from the trees [begin, end) alone, shaped

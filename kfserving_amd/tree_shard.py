@@ -30,7 +30,7 @@ from typing import Callable, List, Optional, Tuple
 
 import numpy as np
 
-from .forest import (OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_CONTRIB_INTERV, OUT_INTERACT, OUT_LEAF, OUT_MARGIN, OUT_PREDICT,
+from .forest import (OUT_CONTRIB, OUT_CONTRIB_APPROX, OUT_CONTRIB_INTERV, OUT_EARLY_STOP, OUT_INTERACT, OUT_LEAF, OUT_MARGIN, OUT_PREDICT,
                      OUT_STAGED, OUT_TREE_QUANTILE, TI_F32, Forest)
 
 
@@ -95,7 +95,7 @@ class TreeShardedForest:
         same rows).  Returns the full output on the root (PREDICT and LEAF
         shaped as DeviceForest.predict returns them, MARGIN [rows, K], CONTRIB
         and CONTRIB_APPROX [rows, K * (F + 1)]) and None elsewhere.
-        OUT_INTERACT, OUT_CONTRIB_INTERV, OUT_TREE_QUANTILE and OUT_STAGED are not served
+        OUT_INTERACT, OUT_CONTRIB_INTERV, OUT_TREE_QUANTILE, OUT_STAGED and OUT_EARLY_STOP are not served
         tree-sharded: each raises ValueError."""
         if kind == OUT_INTERACT:   # it would fall through to the margin path below
             raise ValueError("kind OUT_INTERACT (SHAP interaction values) is not served "
@@ -105,6 +105,8 @@ class TreeShardedForest:
                              "tree-sharded; use DeviceForest.predict")
         if kind == OUT_STAGED:           # a stage end cuts the shards unevenly: not served here
             raise ValueError("kind OUT_STAGED (staged predictions) is not served tree-sharded")
+        if kind == OUT_EARLY_STOP:       # the test reads the sum over all trees so far: no shard has it
+            raise ValueError("kind OUT_EARLY_STOP (prediction early stopping) is not served tree-sharded")
         if kind == OUT_CONTRIB_INTERV:   # no rank's engine holds a background
             raise ValueError("kind OUT_CONTRIB_INTERV (interventional contributions) is not "
                              "served tree-sharded; use DeviceForest.predict")
